@@ -3,12 +3,24 @@
 recordings per GPU, inputs resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode native|reference]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
+A plain run does what the headline figure needs and no more: it synthesises the
+batch, warms up, times the K steps, writes the last timed step's outputs when
+`--dump-outputs DIR` is given (dump_outputs below) and prints the result line.
+`--full` adds everything else the line can carry: the CPU baseline and the
+parity of every file against the oracle, the roofline of the dominant kernel
+and the per-kernel table (their HIP events and an untimed pass of their own),
+the side measurements (PCIe-inclusive step, contexts, exact shortcuts off,
+undecided troughs, real envelopes, host beat stages, drop-in latency) and the
+result gather.  The options of those legs are read only with `--full`.
+
 One process per GPU; files are sharded (weak scaling: every rank processes its
-own 1024 recordings, no data-path collective).  After the timed steps every
-file's raw peaks, final beats and BPM curve go to rank 0 over RCCL (the only
-collective besides the max-time all_reduce).  Rank 0 prints one JSON line.
+own 1024 recordings, no data-path collective).  With `--full`, after the timed
+steps every file's raw peaks, final beats and BPM curve go to rank 0 over RCCL
+(the only collective besides the max-time all_reduce).  Rank 0 prints one JSON
+line.
 
 `python bench.py --gpus N` without WORLD_SIZE in the environment starts the N
 ranks itself (a `torch.distributed.run` child process, before anything touches
@@ -96,7 +108,18 @@ def parse(argv=None):
                          "same stages on the synthetic batch's envelopes (0: skip)")
     ap.add_argument("--cpu-stub", action="store_true",
                     help="TESTS ONLY: oracle-backed detector (tests/bench_stub.py) over gloo on CPU ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: CPU baseline and oracle parity, roofline and per-kernel table, "
+                         "the side measurements and the result gather (their options are read only with this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (rank 0's recordings) as "
+                         "DIR/<name>.npy, float64; a seeded sample of the recordings when they exceed the budget")
     a = ap.parse_args(argv)
+    if not a.full:          # a plain run: set up, warm up, time the steps, dump, report
+        a.no_cpu = True
+        a.pcie_steps = a.contexts = a.exact_steps = a.dropin_files = a.real_env_steps = 0
+        a.host_beat_files = a.parity_files = a.c5_parity_files = 0
+        a.undecided_mult = 0.0
     if a.cpu_stub:          # the side measurements need device memory and streams
         a.pcie_steps = a.contexts = a.exact_steps = a.dropin_files = a.real_env_steps = 0
         a.undecided_mult = 0.0
@@ -346,6 +369,60 @@ def cpu_baseline(mode: str, fs: int, n_frames: int, seed0: int, n_files: int, pa
     return base, parity
 
 
+DUMP_BUDGET = 60 << 20                  # bytes of .npy payload per dump (the files stay under 64 MB in all)
+DUMP_SEED = 2025
+
+
+def dump_sample(sizes, budget: int = DUMP_BUDGET, seed: int = DUMP_SEED):
+    """Positions of the recordings a dump holds in full: a seeded permutation
+    of them, taken while their `sizes` (bytes each) fit the budget, sorted.
+    The same sizes give the same sample in every run and every build."""
+    order = np.random.default_rng(seed).permutation(len(sizes))
+    keep, acc = [], 0
+    for i in order:
+        if acc + int(sizes[i]) > budget:
+            break
+        keep.append(int(i))
+        acc += int(sizes[i])
+    return sorted(keep)
+
+
+def dump_outputs(path: str, host: list, ids) -> dict:
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step (engine.Result.to_host's per-recording dicts `host`, recordings `ids`
+    of the job), as float64 .npy files under `path`:
+
+    n_troughs, n_peaks, flags   of every recording in `host`
+    recording_ids               job-wide index (= synthesis seed) of every recording in `host`
+    sample                      positions in `host` of the recordings held in full below
+                                (all of them when they fit DUMP_BUDGET, else dump_sample's)
+    sample_offsets              [len(sample) + 1] offsets of each sampled recording in env / floor
+    env, floor                  the sampled recordings' envelopes and noise floors, concatenated
+    troughs, peaks              their trough and raw-peak indices, concatenated (counts: n_*[sample])
+
+    Returns {name: element count}."""
+    os.makedirs(path, exist_ok=True)
+
+    def f64(x):
+        return np.asarray(x, dtype=np.float64)
+
+    def cat(key):
+        return np.concatenate([f64(host[i][key]) for i in pick]) if pick else np.zeros(0)
+
+    n_tr = [len(r["troughs"]) for r in host]
+    n_pk = [len(r["peaks"]) for r in host]
+    small = 8 * 6 * (len(host) + 1)                      # the per-recording arrays above
+    sizes = [8 * (2 * len(r["env"]) + a + b) for r, a, b in zip(host, n_tr, n_pk)]
+    pick = dump_sample(sizes, max(0, DUMP_BUDGET - small))
+    arrays = {"n_troughs": f64(n_tr), "n_peaks": f64(n_pk), "flags": f64([r["flags"] for r in host]),
+              "recording_ids": f64(list(ids)), "sample": f64(pick),
+              "sample_offsets": f64(np.concatenate([[0], np.cumsum([len(host[i]["env"]) for i in pick])])),
+              "env": cat("env"), "floor": cat("floor"), "troughs": cat("troughs"), "peaks": cat("peaks")}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {name: int(arr.size) for name, arr in arrays.items()}
+
+
 def shard_seed0(rank: int, files_per_gpu: int) -> int:
     """Weak scaling: rank r synthesises files r*F .. r*F+F-1 (disjoint shards)."""
     return rank * files_per_gpu
@@ -439,6 +516,12 @@ def run_c5(args):
         n_rounds = int(t.item())
     npar = len(mine) if args.c5_parity_files < 0 else args.c5_parity_files
     pick = set(sorted(mine, key=lambda i: lengths[i])[:npar]) if not args.no_cpu else set()
+    # --dump-outputs: a seeded sample of rank 0's recordings, sized by their decimated
+    # lengths (env + floor + at most Nd trough and peak indices each) before any runs
+    dump_ids = set()
+    if args.dump_outputs and rank == 0:
+        dump_ids = {mine[j] for j in dump_sample([8 * 3 * -(-int(lengths[i]) // d.ds) for i in mine])}
+    need_host = args.full or bool(dump_ids)
     kept, rows, kprof = {}, [], {}
     ties_c5 = [0]                       # recordings the steps' tie checks re-decided
     frames = nd_tot = 0
@@ -482,13 +565,16 @@ def run_c5(args):
                         with torch.cuda.stream(st):
                             ties_c5[0] += dets[sub[0]].tie_check_finish(h, sub[4], params, 7, args.options)
 
-            # per-kernel profile: the sub-batches one after another (untimed)
+            # warmup, the sub-batches one after another (untimed); --full: with the per-kernel profile
             for sub in subs:
                 dk = dets[sub[0]]
-                dk.profile(True)
+                if args.full:
+                    dk.profile(True)
                 for _ in range(max(1, args.warmup)):
                     run_sub(sub)
                 sync(dk)
+                if not args.full:
+                    continue
                 dk.profile(False)
                 for kn, (c, t) in dk.profile_read().items():
                     c0, t0 = kprof.get(kn, (0, 0.0))
@@ -507,11 +593,11 @@ def run_c5(args):
             dist.barrier()
         elapsed += time.perf_counter() - t0
         if idx:
-            for k, gi, fo, pcm, out in subs:
+            for k, gi, fo, pcm, out in subs if need_host else ():
                 host = out.to_host()
                 for j, i in enumerate(gi):
                     rows.append(FileResult(i, raw_peaks=host[j]["peaks"], flags=host[j]["flags"]))
-                    if i in pick:
+                    if i in pick or i in dump_ids:
                         kept[i] = {kk: (v.copy() if isinstance(v, np.ndarray) else v) for kk, v in host[j].items()}
                 del host
             del subs, step
@@ -545,7 +631,13 @@ def run_c5(args):
             parity.update(files=c[0], peaks_equal=c[1], troughs_equal=c[2], flags_equal=c[3],
                           ok=c[4] == 0, ranks=world, ties_unresolved=c[5], ties_resolved=c[6],
                           tie_flagged_in_steps=c[7])
-    allres = gather_file_results(rows, len(lengths), device=det.device if (world > 1 and backend == "nccl") else None)
+    dumped = None
+    if dump_ids:
+        dumped = dump_outputs(args.dump_outputs, [kept[i] for i in sorted(dump_ids)], sorted(dump_ids))
+    allres = []
+    if args.full:
+        allres = gather_file_results(rows, len(lengths),
+                                     device=det.device if (world > 1 and backend == "nccl") else None)
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         total = int(lengths.sum()) * ch
@@ -576,10 +668,11 @@ def run_c5(args):
                 "pipeline": {"hbm_bytes_per_step": step_bytes,
                              "achieved_GBps": round(step_bytes / (ms / 1e3) / 1e9, 1),
                              "frac_of_peak": round(step_bytes / (ms / 1e3) / 1e9 / (HBM_PEAK_GBS * world), 5)},
-                "parity": parity, "kernels_rank0": kernels,
+                "full": bool(args.full), "dumped_outputs": dumped,
+                "parity": parity, "kernels_rank0": kernels if args.full else None,
                 "result_gather": {"files": sum(1 for r in allres if r is not None),
                                   "peaks": int(sum(len(r["raw_peaks"]) for r in allres
-                                                   if r is not None and "raw_peaks" in r))}}
+                                                   if r is not None and "raw_peaks" in r))} if args.full else None}
         print(json.dumps(line), flush=True)
     for x in dets[1:]:
         x.close()
@@ -682,17 +775,21 @@ def main(args):
         return outs_pp[(k_steps - 1) & 1] if k_steps > 0 else out
 
     abytes = algorithmic_bytes(args.mode, F, n, nd, d.ds)
-    # warmup with every launch bracketed by events: picks the dominant kernel
-    det.profile(True)
+    # --full: warmup with every launch bracketed by events, which picks the
+    # dominant kernel (a plain run records no events at all)
+    if args.full:
+        det.profile(True)
     run_steps(args.warmup)
     sync(det)
-    det.profile(False)
-    wprof = {k: v for k, v in det.profile_read().items() if k in abytes}
+    wprof = {}
+    if args.full:
+        det.profile(False)
+        wprof = {k: v for k, v in det.profile_read().items() if k in abytes}
     dom = max(wprof, key=lambda k: wprof[k][1]) if wprof else ""
     if world > 1:
         dist.barrier()
-    # timed steps: events around the dominant kernel's launches only, so the
-    # step time carries no per-launch event overhead
+    # timed steps: with --full, events around the dominant kernel's launches
+    # only, so the step time carries no per-launch event overhead
     # Reference mode's envelope is a few waves of sequential passes, so a
     # stream of batches runs batch k+1's envelope beside batch k's detection
     # (engine.BatchPipeline, two contexts on two streams): a step is still one
@@ -707,10 +804,11 @@ def main(args):
             pipe.submit(pcm)
         pipe.finish()
         pipe.ties_resolved = 0
-        for x in (pipe.env_det, pipe.det_det):
-            x.profile_only(dom)
-            x.profile(True)
-    else:
+        if args.full:
+            for x in (pipe.env_det, pipe.det_det):
+                x.profile_only(dom)
+                x.profile(True)
+    elif args.full:
         det.profile_only(dom)
         det.profile(True)
     sync(det)
@@ -726,32 +824,37 @@ def main(args):
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    prof = {}
     if piped:
-        prof = {}
-        for x in (pipe.env_det, pipe.det_det):
+        for x in (pipe.env_det, pipe.det_det) if args.full else ():
             x.profile(False)
             for k, (c, tms) in x.profile_read().items():
                 c0, t_0 = prof.get(k, (0, 0.0))
                 prof[k] = (c0 + c, t_0 + tms)
         ties["raised"] = pipe.ties_resolved
-    else:
+    elif args.full:
         det.profile(False)
         prof = det.profile_read()
-    gpu_host = last.to_host()          # the timed steps' outputs (checked against the oracle below)
+    # the last timed step's outputs: dumped, and with --full checked against the oracle below
+    gpu_host = last.to_host() if args.full or args.dump_outputs else None
     ties_timed = dict(ties)
     if pipe is not None:
         pipe.close()
         del pipe
     elapsed, total_peaks = reduce_results(t1 - t0, out.n_peaks, world, rank)
-    # per-kernel table from a separate, untimed pass with every launch bracketed
-    det.profile_only("")
-    det.profile(True)
-    kprof_steps = max(3, min(args.steps, 10))
-    for _ in range(kprof_steps):
-        step()
-    sync(det)
-    det.profile(False)
-    kprof = det.profile_read()
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, gpu_host, range(seed0, seed0 + F))
+    # --full: per-kernel table from a separate, untimed pass with every launch bracketed
+    kprof, kprof_steps = {}, max(3, min(args.steps, 10))
+    if args.full:
+        det.profile_only("")
+        det.profile(True)
+        for _ in range(kprof_steps):
+            step()
+        sync(det)
+        det.profile(False)
+        kprof = det.profile_read()
 
     # PCIe-inclusive rate: the same step with the PCM handed over in
     # pinned host memory and copied to HBM inside the timed region.  Reported
@@ -991,7 +1094,8 @@ def main(args):
     # 8(e)): raw peaks of every file, and final beats + the smoothed BPM curve of
     # the files whose beat stages ran.
     from bpm_analysis_amd.shard import FileResult, gather_file_results
-    rows = [FileResult(seed0 + f, raw_peaks=gpu_host[f]["peaks"], flags=gpu_host[f]["flags"]) for f in range(F)]
+    rows = [FileResult(seed0 + f, raw_peaks=gpu_host[f]["peaks"], flags=gpu_host[f]["flags"])
+            for f in range(F if args.full else 0)]
     host_beats = None
     if args.host_beat_files > 0:
         from bpm_analysis_amd import beats
@@ -1020,9 +1124,9 @@ def main(args):
                                  "final_beats": int(sum(len(r["final_peaks"]) for r in done if "error" not in r))},
                       "native_equals_python": bool(same)}
     tg0 = time.perf_counter()
-    allres = gather_file_results(rows, total_files, device=cdev if world > 1 else None)
+    allres = gather_file_results(rows, total_files, device=cdev if world > 1 else None) if args.full else None
     gathered = None
-    if rank == 0:
+    if rank == 0 and args.full:
         got = [r for r in allres if r is not None]
         gathered = {"ranks": world, "files": len(got), "peaks": int(sum(len(r["raw_peaks"]) for r in got)),
                     "bpm_curves": int(sum(1 for r in got if len(r["bpm"]))),
@@ -1100,7 +1204,9 @@ def main(args):
                        "batch_pipeline": bool(piped)},
             "roofline": roof, "cpu_baseline": cpu, "parity": parity,
             "gpu_vs_cpu": (value / cpu["value"]) if cpu else None,
-            "pipeline": pipeline, "pcie_inclusive": pcie, "kernels": kernels, "total_raw_peaks": total_peaks,
+            "full": bool(args.full), "dumped_outputs": dumped,
+            "pipeline": pipeline, "pcie_inclusive": pcie, "kernels": kernels if args.full else None,
+            "total_raw_peaks": total_peaks,
             "result_gather": gathered, "multi_context": multi, "exact_no_shortcuts": exact,
             "host_beat_stages": host_beats, "dropin_latency": dropin, "draft_undecided": undecided,
             "real_envelope_detection": real,

@@ -195,12 +195,14 @@ def _bench_json(stdout: str) -> dict:
 def test_bench_launches_n_ranks(workload):
     """`python bench.py --gpus 2` starts two ranks itself (torch.distributed.run
     child, gloo under --cpu-stub), reports n_gpus 2 and gathers both ranks'
-    files to rank 0; parity and the CPU baseline are kept at N > 1."""
+    files to rank 0; parity and the CPU baseline are kept at N > 1 (the legs
+    of `--full`)."""
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--cpu-stub", "--steps", "1", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--cpu-stub", "--steps", "1", "--warmup", "1",
+           "--full"]
     if workload == "metric":
         cmd += ["--files", "3", "--secs", "6", "--parity-files", "2", "--host-beat-files", "1"]
     elif workload == "strong":   # BASELINE C4's shape (--files-total over the ranks), 5 recordings in the job

@@ -12,6 +12,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -5 gpurun_out/pt.log
 [ $rc -eq 0 ] || exit 1
 for lib in build_var/libbpmx_head.so bpm_analysis_amd/libbpmx.so build_var/libbpmx_head.so bpm_analysis_amd/libbpmx.so; do
-  BPMX_LIB=$lib timeout -k 10 300 python bench.py --pcie-steps 0 --contexts 0 --exact-steps 0 --host-beat-files 0 > gpurun_out/b.log 2>&1 || exit 1
-  grep "^{" gpurun_out/b.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['ms_per_step'],4), d['parity']['ok'], {k:v['avg_ms'] for k,v in d['kernels'].items() if v['avg_ms']>0.05})"
+  blog=$(mktemp)
+  BPMX_LIB=$lib timeout -k 10 300 python bench.py --full --pcie-steps 0 --contexts 0 --exact-steps 0 --host-beat-files 0 > "$blog" 2>&1 || exit 1
+  grep "^{" "$blog" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', round(d['ms_per_step'],4), d['parity']['ok'], {k:v['avg_ms'] for k,v in d['kernels'].items() if v['avg_ms']>0.05})"
 done

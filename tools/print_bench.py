@@ -1,3 +1,4 @@
+# Digest of a `python bench.py --full` log (the fields below are null in a plain run's line).
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print(d["ms_per_step"], d["value"], d["parity"]["ok"] if d["parity"] else None, d["roofline"]["frac"])
