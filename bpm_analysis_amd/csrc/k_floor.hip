@@ -245,11 +245,16 @@ __global__ __launch_bounds__(T) void k_rolling_quantile(RollqArgs A) {
             if (lane == 0) wpre[w] = __popcll(word);
         }
         __syncthreads();
-        if (wid == 0) {
-            int c = lane < nwords ? wpre[lane] : 0, x = c;
-            for (int o = 1; o < 64; o <<= 1) { int y = __shfl_up(x, o); if (lane >= o) x += y; }
-            if (lane < nwords) wpre[lane] = x - c;
-            if (lane == 63) s_nE = x;
+        if (wid == 0) {                                  /* exclusive scan of the word counts: up to cap / 64 words */
+            int run = 0;
+            for (int w0 = 0; w0 < nwords; w0 += 64) {
+                const int c = w0 + lane < nwords ? wpre[w0 + lane] : 0;
+                int x = c;
+                for (int o = 1; o < 64; o <<= 1) { int y = __shfl_up(x, o); if (lane >= o) x += y; }
+                if (w0 + lane < nwords) wpre[w0 + lane] = run + x - c;
+                run += __shfl(x, 63);
+            }
+            if (lane == 0) s_nE = run;
         }
         __syncthreads();
         for (int w = wid; w < nwords; w += T / 64) {
@@ -301,7 +306,10 @@ __global__ __launch_bounds__(T) void k_rolling_quantile(RollqArgs A) {
         }
         const int qa = (int)k + m;
         int qb = qa + 1;
-        if (valid && nobs > 1) {   /* next valid sorted index after qa: skip excluded positions */
+        /* next valid sorted index after qa (skip excluded positions), only where
+         * the output interpolates: with k == idxf at the window's last sample
+         * (q = 1) there is none, and the search would leave the union */
+        if (valid && nobs > 1 && (double)k != idxf) {
             for (;;) {
                 const int rel = (int)(uint16_t)(Ap[qb] - p16);
                 if (rel >= xlo && rel < xhi) break;
@@ -551,7 +559,7 @@ __global__ __launch_bounds__(T) void k_rolling_quantile_g(RollqArgs A) {
         }
         const int64_t qa = k + m;
         int64_t qb = qa + 1;
-        if (valid && nobs > 1) {
+        if (valid && nobs > 1 && (double)k != idxf) {      /* as in k_rolling_quantile: none after the last (q = 1) */
             for (;;) {
                 const int64_t rel = Ap[qb] - P0;
                 if (rel >= xlo && rel < xhi) break;

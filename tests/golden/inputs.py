@@ -148,7 +148,46 @@ def env_cases() -> dict:
     out["env_random_long_window"] = (r, sr, dict(noise_window_sec=20))
     r2 = np.abs(np.convolve(rng.standard_normal(9000), np.ones(9) / 9.0, mode="same")) * 100.0 + 1.0
     out["env_random_rough"] = (r2, sr, None)
+    out.update(param_env_cases())
     out.update(tie_env_cases())
+    return out
+
+
+def sec_for(k: int, sr: int) -> float:
+    """A `*_sec` setting that the reference's ``int(sec * sr)`` turns into exactly k."""
+    return (k + 0.5) / sr
+
+
+def param_env_cases() -> dict:
+    """Tie-free envelopes with the five detection settings off their defaults:
+    find_peaks' distance (1: the distance filter is skipped; 453: most
+    candidates have a higher neighbour hundreds of candidates away), the noise
+    window (3: NaN edges that bfill / ffill closes; 151 with the median), the
+    noise-floor level at both ends, distinct prominence levels, and a static
+    floor whose level equals the all-NaN fallback's (0.1)."""
+    sr = 302
+    out = {}
+
+    def beat(n, period=250.0):
+        return np.maximum(0.0, np.sin(2 * np.pi * np.arange(n) / period)) ** 8
+
+    rng = np.random.default_rng(20251)
+    out["env_params_distance1"] = (rng.random(3500) ** 3 * 1000 + 50 * beat(3500), sr,
+                                   dict(min_peak_distance_sec=sec_for(1, sr)))
+    out["env_params_distance453"] = (rng.random(4000) ** 3 * 1000 + 50 * beat(4000), sr,
+                                     dict(min_peak_distance_sec=sec_for(453, sr)))
+    out["env_params_window3"] = (300 * beat(3200) + rng.random(3200) + 20, sr,
+                                 dict(noise_window_sec=sec_for(3, sr)))
+    out["env_params_window151_q50"] = (300 * beat(3700, 180.0) + 40 * rng.random(3700) + 20, sr,
+                                       dict(noise_window_sec=sec_for(151, sr), noise_floor_quantile=0.5))
+    out["env_params_q0"] = (200 + 80 * np.sin(np.arange(3300) / 300.0) + 300 * beat(3300) + rng.random(3300), sr,
+                            dict(noise_floor_quantile=0.0))
+    out["env_params_q1_levels"] = (10.0 + 0.05 * np.arange(3900) + 900 * beat(3900) + 30 * rng.random(3900), sr,
+                                   dict(noise_floor_quantile=1.0, trough_prominence_quantile=0.3,
+                                        peak_prominence_quantile=0.02))
+    pos = [0, 500, 1100, 1800, 2300, 2999]
+    val = [15.0, 950.0, 45.0, 1010.0, 25.0, 820.0]
+    out["env_params_static_q10"] = (_vshape(pos, val, 3000), sr, dict(noise_floor_quantile=0.1))
     return out
 
 

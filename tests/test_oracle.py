@@ -128,6 +128,116 @@ def test_tie_report_is_exact():
         assert tie == (len(outcomes) > 1), (x.tolist(), dist)
 
 
+def _grid_envelopes():
+    """Three seeded 6000-sample envelopes without equal values (checked by the
+    test): rough, beats on noise, a slow wander."""
+    rng = np.random.default_rng(302)
+    n = 6000
+    t = np.arange(n)
+    beat = np.maximum(0.0, np.sin(2 * np.pi * t / 250.0)) ** 8
+    return [rng.random(n) ** 3 * 1000 + 50 * beat,
+            300 * beat + rng.random(n) + 20,
+            200 + 80 * np.sin(t / 700.0) + 300 * beat + rng.random(n)]
+
+
+GRID_DISTANCES = [1, 2, 3, 15, 40, 128, 129, 300, 906, 7000]
+GRID_LEVELS = [0.0, 0.05, 0.2, 0.5, 0.9, 0.999, 1.0]
+
+
+def _grid_windows(n):
+    return [3, 4, 5, 6, 63, 64, 65, 151, 302, 3019, 3020, n - 1, n, n + 1, 2 * n + 1, 20000]
+
+
+def test_oracle_matches_libraries_off_the_defaults():
+    """The oracle's find_peaks, interp_dense + rolling_quantile and quantile
+    against the library calls the reference makes (scipy.signal.find_peaks,
+    pandas' reindex + interpolate, which leaves NaN before the first trough,
+    its centred rolling quantile with bfill / ffill, np.quantile), bit for
+    bit, over distances, windows and levels far from the defaults: distance 1
+    (no filter) to beyond the envelope, windows of 3-5 samples (NaN edges),
+    even and odd, up to more than twice the envelope, levels 0, 1 and close
+    to 1."""
+    import pandas as pd
+    from scipy.signal import find_peaks
+    for env in _grid_envelopes():
+        n = env.size
+        assert np.unique(env).size == n                     # no equal heights: the tie order decides nothing
+        prom = float(np.quantile(env, 0.1))
+        for q in GRID_LEVELS:
+            assert O.quantile(env, q) == np.quantile(env, q)
+        for dist in GRID_DISTANCES:
+            for neg in (False, True):
+                x = -env if neg else env
+                for kw in (dict(distance=dist), dict(distance=dist, prominence=prom)):
+                    got, tie = O.find_peaks(env, negate=neg, return_tie=True, **kw)
+                    assert np.array_equal(got, find_peaks(x, **kw)[0]), (dist, neg, kw)
+                    assert not tie
+            floor = np.full(n, np.quantile(env, 0.3))
+            assert np.array_equal(O.find_peaks(env, height=floor, distance=dist, prominence=prom),
+                                  find_peaks(env, height=floor, distance=dist, prominence=prom)[0])
+        for dist in (2, 15, 300):
+            tr = find_peaks(-env, distance=dist, prominence=prom)[0]
+            dense = O.interp_dense(tr, env)
+            s = pd.Series(index=tr, data=env[tr]).reindex(np.arange(n)).interpolate()
+            assert np.isnan(s.values[:tr[0]]).all() and not np.isnan(s.values[tr[0]:]).any()
+            assert np.array_equal(dense, s.values, equal_nan=True)
+            for w in _grid_windows(n):
+                roll = s.rolling(window=w, min_periods=3, center=True)
+                for q in GRID_LEVELS:
+                    want = roll.quantile(q).bfill().ffill().values
+                    assert np.array_equal(O.rolling_quantile(dense, w, 3, q), want, equal_nan=True), (dist, w, q)
+
+
+@pytest.mark.parametrize("name", G.names(kind="env", prefix="env_params"))
+def test_param_fixtures_exact_settings_and_tie_free(name):
+    """The env_params_* fixtures: the `*_sec` settings give the intended
+    integers through both derivations (the oracle's and the package's), at
+    least one setting is off its default, and no height tie decides anything
+    (numpy's argsort order and the stable order give the same troughs, floor
+    and peaks), so the reference's recorded outputs pin one answer."""
+    from bpm_analysis_amd import design
+    from tests.golden import inputs as I
+    g = G.load(name)
+    env, p, sr = g["env"], g["params"], int(g["sr"])
+    d = G.env_derived(g)
+    dd = design.detect_design(sr, p)
+    assert (dd.distance, dd.noise_window) == (d.distance, d.noise_window)
+    over = I.env_cases()[name][2]
+    want = {"min_peak_distance_sec": d.distance, "noise_window_sec": d.noise_window}
+    for key, got in want.items():
+        if key in over:
+            assert over[key] == I.sec_for(got, sr)
+    assert over and all(p[k] != G.BASE_PARAMS[k] for k in over)
+    raw, ttie = O.find_peaks(env, distance=d.distance, negate=True, return_tie=True,
+                             prominence=O.quantile(env, p["trough_prominence_quantile"]))
+    floor, tr, flags = O.noise_floor(env, d, p)
+    pk, ptie = O.raw_peaks(env, floor, d, p, return_tie=True)
+    assert not ttie and not ptie
+    nf, nt, nfl, nraw = O.noise_floor_numpy_order(env, d, p)
+    assert np.array_equal(nraw, raw) and np.array_equal(nt, tr) and np.array_equal(nf, floor, equal_nan=True)
+    npk = O.find_peaks_numpy_order(env, height=floor, distance=d.distance,
+                                   prominence=O.quantile(env, p["peak_prominence_quantile"]))
+    assert np.array_equal(npk, pk)
+
+
+def test_param_fixtures_reach_their_branches():
+    """What each env_params_* fixture is for, read off the reference's outputs."""
+    g = {n: G.load(n) for n in G.names(kind="env", prefix="env_params")}
+    d = {n: G.env_derived(v) for n, v in g.items()}
+    assert len(g) == 7
+    assert d["env_params_distance1"].distance == 1
+    assert np.min(np.diff(g["env_params_distance1"]["peaks"])) < 15      # closer than the default distance keeps
+    assert d["env_params_distance453"].distance == 453
+    assert d["env_params_window3"].noise_window == 3 and not np.isnan(g["env_params_window3"]["floor"]).any()
+    w = g["env_params_window151_q50"]
+    assert d["env_params_window151_q50"].noise_window == 151 and w["params"]["noise_floor_quantile"] == 0.5
+    assert g["env_params_q0"]["params"]["noise_floor_quantile"] == 0.0
+    assert g["env_params_q1_levels"]["params"]["noise_floor_quantile"] == 1.0
+    s = g["env_params_static_q10"]
+    assert int(s["flags"]) == 1 and len(s["troughs"]) < 5
+    assert np.all(s["floor"] == np.quantile(s["env"], 0.1))
+
+
 def test_oracle_vulpine_known_answer():
     """Labeler-recipe envelope of the committed filtered WAV reproduces every raw
     peak index of samples/vulpine_Debug_Log.md (heartbeat_labeler.py:63-67)."""
