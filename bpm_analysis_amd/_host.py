@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 
 import numpy as np
 
@@ -98,6 +99,51 @@ def beats(env: np.ndarray, sr: int, floor, raw_peaks: np.ndarray, params, hint=N
     return {"final_peaks": fin[:nf.value].copy(), "bpm_times": bt[:nb.value].copy(), "bpm": bv[:nb.value].copy(),
             "start_bpm": float(pas[0]), "peak_time": nan2none(pas[1]), "recovery_time": nan2none(pas[2]),
             "tags": tags[:len(pk)].copy()}
+
+
+class _Scratch(threading.local):
+    """Per-thread env / floor stand-ins for beats_packed: NaN everywhere
+    between calls, grown on demand."""
+
+    def __init__(self):
+        self.env = np.full(0, np.nan)
+        self.floor = np.full(0, np.nan)
+
+
+_scratch = _Scratch()
+
+
+def packed_scratch_is_nan() -> bool:
+    """True when this thread's beats_packed scratch holds nothing but NaN (it
+    must, after every call)."""
+    return bool(np.isnan(_scratch.env).all() and np.isnan(_scratch.floor).all())
+
+
+def beats_packed(peaks: np.ndarray, env_pk: np.ndarray, floor_pk: np.ndarray, n_env: int, sr: int, params,
+                 hint=None) -> dict:
+    """``beats`` from a packed result (engine.Packed.to_host): the raw peaks and
+    the envelope and floor at those peaks only, of a recording of ``n_env``
+    decimated samples.  The beat stages read env and floor nowhere else, so
+    bpmx_beats runs on this thread's scratch arrays, NaN except at the peaks:
+    O(n_peaks) per file to fill and to clear, and a read anywhere else would
+    come out as a wrong result instead of passing unnoticed."""
+    pk = np.ascontiguousarray(peaks, dtype=np.int64)
+    n_env = int(n_env)
+    if len(pk) and (pk.min() < 0 or pk.max() >= n_env):
+        raise ValueError("beats_packed: peak index outside the recording")
+    if len(env_pk) != len(pk) or len(floor_pk) != len(pk):
+        raise ValueError("beats_packed: env_pk and floor_pk need one value per peak")
+    s = _scratch
+    if s.env.size < n_env:
+        size = max(n_env, 2 * s.env.size)
+        s.env, s.floor = np.full(size, np.nan), np.full(size, np.nan)
+    s.env[pk] = env_pk
+    s.floor[pk] = floor_pk
+    try:
+        return beats(s.env[:n_env], sr, s.floor[:n_env], pk, params, hint)
+    finally:
+        s.env[pk] = np.nan
+        s.floor[pk] = np.nan
 
 
 def beats_batch(results, params, hint=None, threads: int = 1) -> list:

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # BPMX_LIB: another build of the same library (diagnostic A/B runs of kernel variants)
 LIB_PATH = os.environ.get("BPMX_LIB") or os.path.join(_HERE, "libbpmx.so")
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 DT_U8, DT_I16, DT_I32, DT_F32, DT_F64 = 0, 1, 2, 3, 4
 MODE_REFERENCE, MODE_NATIVE = 0, 1
@@ -40,7 +40,7 @@ STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 
 EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy", "bpmx_decimated_length",
-           "bpmx_run", "bpmx_run_ordered", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
+           "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
            "bpmx_stats", "bpmx_set_pipeline"]
 
 
@@ -72,6 +72,16 @@ class PeakOrder(ctypes.Structure):
     export and the caller's visiting ranks (device pointers or None)."""
     _fields_ = [("cand", ctypes.c_void_p * 2), ("n_cand", ctypes.c_void_p * 2),
                 ("rank", ctypes.c_void_p * 2), ("use_rank", ctypes.c_void_p * 2)]
+
+
+class PackedOut(ctypes.Structure):
+    """bpmx_packed: the ragged per-peak / per-trough tables and the int16 debug
+    samples bpmx_pack writes (device pointers; None leaves that part out)."""
+    _fields_ = [("cap_peaks", ctypes.c_int64), ("cap_troughs", ctypes.c_int64),
+                ("pk_off", ctypes.c_void_p), ("tr_off", ctypes.c_void_p),
+                ("pk_idx", ctypes.c_void_p), ("pk_env", ctypes.c_void_p), ("pk_floor", ctypes.c_void_p),
+                ("tr_idx", ctypes.c_void_p), ("tr_env", ctypes.c_void_p),
+                ("y16", ctypes.c_void_p), ("y_max", ctypes.c_void_p)]
 
 
 class BpmxError(RuntimeError):
@@ -121,6 +131,9 @@ def load() -> ctypes.CDLL:
     L.bpmx_run_ordered.argtypes = [P, ctypes.POINTER(Params), ctypes.POINTER(Batch), ctypes.POINTER(Out),
                                    ctypes.POINTER(PeakOrder), P]
     L.bpmx_run_ordered.restype = ctypes.c_int
+    L.bpmx_pack.argtypes = [P, I32, ctypes.POINTER(ctypes.c_int64), I32, ctypes.POINTER(Out),
+                            ctypes.POINTER(PackedOut), P]
+    L.bpmx_pack.restype = ctypes.c_int
     L.bpmx_synth.argtypes = [P, U64, I32, ctypes.POINTER(ctypes.c_int64), I32, I32, P, P]
     L.bpmx_synth.restype = ctypes.c_int
     L.bpmx_synth_host.argtypes = [U64, I64, I32, I32, P]

@@ -714,6 +714,26 @@ def analyze_fast(results: Sequence[Dict], params: Dict, start_bpm_hint: Optional
     dict(final_peaks, bpm_times, bpm, start_bpm, peak_time, recovery_time,
     tags), or the entry's / the stage's ``error``.  The same beats and curve
     as ``analyze_recording`` (tests/test_host_beats.py); HRV, slopes, reports
-    and the plot stay with analyze_recording."""
+    and the plot stay with analyze_recording.
+
+    Packed per-file dicts (engine.Packed.to_host: ``env_pk`` / ``floor_pk`` at
+    the raw peaks instead of whole arrays) run through ``_host.beats_packed``
+    on ``threads`` Python threads (ctypes releases the GIL around the call)."""
     from . import _host
-    return _host.beats_batch(list(results), params, start_bpm_hint, threads=threads)
+    results = list(results)
+    if not any("env_pk" in r for r in results):
+        return _host.beats_batch(results, params, start_bpm_hint, threads=threads)
+    bp = _host.beat_params(params)
+
+    def one(r):
+        if "error" in r:
+            return r
+        if "env_pk" in r:
+            return _host.beats_packed(r["peaks"], r["env_pk"], r["floor_pk"], r["n_env"], r["sr"], bp, start_bpm_hint)
+        return _host.beats(r["env"], r["sr"], r["floor"], r["peaks"], bp, start_bpm_hint)
+
+    if threads <= 1 or len(results) < 2:
+        return [one(r) for r in results]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(threads) as ex:
+        return list(ex.map(one, results))

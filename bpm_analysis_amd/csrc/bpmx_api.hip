@@ -1155,4 +1155,66 @@ int bpmx_run(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpm
     return rc;
 }
 
+int bpmx_pack(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, const bpmx_out *in,
+              const bpmx_packed *out, void *stream) {
+    if (!ctx || !frame_offsets || !in || !out) return fail(BPMX_E_ARG, "bpmx_pack: NULL argument");
+    const int F = n_files;
+    if (F < 1 || ds < 1) return fail(BPMX_E_ARG, "bpmx_pack: bad n_files/ds");
+    const bool tab[2] = {out->pk_off != nullptr, out->tr_off != nullptr};
+    const bool y16 = out->y16 != nullptr;
+    if (!tab[0] && !tab[1] && !y16) return fail(BPMX_E_ARG, "bpmx_pack: nothing to pack");
+    if (tab[0] && (!in->peaks || !in->n_peaks || !in->env || !in->floor || !out->pk_idx || !out->pk_env ||
+                   !out->pk_floor || out->cap_peaks < 0))
+        return fail(BPMX_E_ARG, "bpmx_pack: the peak table needs peaks, n_peaks, env, floor and its three arrays");
+    if (tab[1] && (!in->troughs || !in->n_troughs || !in->env || !out->tr_idx || !out->tr_env || out->cap_troughs < 0))
+        return fail(BPMX_E_ARG, "bpmx_pack: the trough table needs troughs, n_troughs, env and its two arrays");
+    if (y16 && (!in->y || !out->y_max)) return fail(BPMX_E_ARG, "bpmx_pack: y16 needs y and y_max");
+    std::vector<int64_t> doff((size_t)F + 1);
+    int64_t maxnd = 0;
+    doff[0] = 0;
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = frame_offsets[f + 1] - frame_offsets[f];
+        if (n < 0) return fail(BPMX_E_ARG, "frame offsets must be non-decreasing");
+        const int64_t nd = bpmx_decimated_length(n, ds);
+        if (nd >= (int64_t)INT_MAX / 2) return fail(BPMX_E_LIMIT, "recording too long");
+        doff[f + 1] = doff[f] + nd;
+        maxnd = std::max(maxnd, nd);
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = BPMX_OK;
+    bool grew = false;
+    int64_t *d_doff = (int64_t *)ctx->buf("pack_geo", doff.size() * 8, &rc, &grew);
+    if (rc != BPMX_OK) return rc;
+    if (grew || doff != ctx->pack_key) {
+        /* stream-ordered: launches of an earlier pack still read the old offsets */
+        ctx->pack_key.swap(doff);
+        HIP_TRY(hipMemcpyAsync(d_doff, ctx->pack_key.data(), ctx->pack_key.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    if (tab[0] || tab[1]) {
+        PackArgs a{};
+        a.doff = d_doff; a.n_files = F; a.env = in->env; a.floor = in->floor;
+        if (tab[0]) {
+            a.cnt[0] = in->n_peaks; a.idx[0] = in->peaks; a.off[0] = out->pk_off; a.cap[0] = out->cap_peaks;
+            a.oidx[0] = out->pk_idx; a.oenv[0] = out->pk_env; a.ofloor = out->pk_floor;
+        }
+        if (tab[1]) {
+            a.cnt[1] = in->n_troughs; a.idx[1] = in->troughs; a.off[1] = out->tr_off; a.cap[1] = out->cap_troughs;
+            a.oidx[1] = out->tr_idx; a.oenv[1] = out->tr_env;
+        }
+        LAUNCH(ctx, s, "k_pack_scan", k_pack_scan, dim3(2), dim3(PK_SCAN_T), 0, s, a);
+        LAUNCH(ctx, s, "k_pack_gather", k_pack_gather, dim3(F, 2), dim3(PK_GATHER_T), 0, s, a);
+    }
+    if (y16) {
+        Y16Args a{};
+        a.doff = d_doff; a.y = in->y; a.ymax = (unsigned long long *)out->y_max; a.y16 = out->y16;
+        HIP_TRY(hipMemsetAsync(out->y_max, 0, (size_t)F * 8, s));
+        /* a few elements (quant: pairs) per thread; the second grid dimension is a 16-bit one */
+        const unsigned gm = (unsigned)std::min<int64_t>(std::max<int64_t>((maxnd + PK_Y16_T * 8 - 1) / (PK_Y16_T * 8), 1), 65535);
+        LAUNCH(ctx, s, "k_y16_max", k_y16_max, dim3(F, gm), dim3(PK_Y16_T), 0, s, a);
+        LAUNCH(ctx, s, "k_y16_quant", k_y16_quant, dim3(F, gm), dim3(PK_Y16_T), 0, s, a);
+    }
+    return BPMX_OK;
+}
+
 }  // extern "C"

@@ -37,6 +37,7 @@ struct bpmx_ctx {
     void *lf = nullptr;                            /* k_longfft.hip's plan state (LfHost) */
     std::map<std::string, std::pair<void *, size_t>> bufs;
     std::vector<int64_t> g_key;   /* geometry of the last upload */
+    std::vector<int64_t> pack_key; /* decimated offsets in "pack_geo" (bpmx_pack; also the upload's host source) */
     /* native-mode block-state tables (host copies back the async uploads) */
     std::vector<int64_t> nat_key;
     std::vector<double> nat_tab;

@@ -508,6 +508,31 @@ template <bool PRUNE>
 __global__ void k_rollq_wm_t(RollqArgs A, uint16_t *pos_scratch, int32_t *full);
 __global__ void k_floor_wm(FloorWmArgs A);
 
+/* bpmx_pack (k_pack.hip): table w = 0 is the raw peaks', 1 the troughs' */
+enum { PK_SCAN_T = 1024, PK_GATHER_T = 128, PK_Y16_T = 256 };
+struct PackArgs {
+    const int64_t *doff;        /* [F+1] decimated offsets */
+    int32_t n_files;
+    const int32_t *cnt[2];      /* [F] n_peaks / n_troughs */
+    const int64_t *idx[2];      /* peaks / troughs, per-file slices at D_f */
+    const double *env, *floor;
+    int64_t *off[2];            /* out [F+1]; null: table w is not built */
+    int64_t cap[2];
+    int32_t *oidx[2];
+    double *oenv[2];
+    double *ofloor;             /* peak table only */
+};
+struct Y16Args {
+    const int64_t *doff;
+    const double *y;
+    unsigned long long *ymax;   /* [F] bits of max|y|, zeroed before k_y16_max */
+    int16_t *y16;
+};
+__global__ void k_pack_scan(PackArgs A);
+__global__ void k_pack_gather(PackArgs A);
+__global__ void k_y16_max(Y16Args A);
+__global__ void k_y16_quant(Y16Args A);
+
 }  // namespace bpmx
 
 #endif

@@ -78,11 +78,15 @@ def _read_wav(file_path: str):
         return wavfile.read(file_path)
 
 
-def _write_debug_wav(path: str, sr: int, y: np.ndarray) -> None:
-    """np.int16(y / max|y| * 32767) at rate sr (bpm_analysis.py:1047-1050, :1056-1060)."""
+def _write_debug_wavs(file_path: str, output_directory: str, sr: int, y16: np.ndarray) -> None:
+    """Both debug WAVs of the reference (next to the input, :1047-1050, and in
+    the output directory, :1056-1060) from the samples the device quantised
+    (bpmx_pack's y16: np.int16(y / np.max(np.abs(y)) * 32767), value for value)."""
     from scipy.io import wavfile
-    with np.errstate(invalid="ignore", divide="ignore"):
-        wavfile.write(path, sr, np.int16(y / np.max(np.abs(y)) * 32767))
+    y16 = np.ascontiguousarray(y16, dtype=np.int16)
+    wavfile.write(f"{os.path.splitext(file_path)[0]}_filtered_debug.wav", sr, y16)
+    base = os.path.basename(os.path.splitext(file_path)[0])
+    wavfile.write(os.path.join(output_directory, f"{base}_filtered_debug.wav"), sr, y16)
 
 
 # ---------------------------------------------------------------- one GPU run per file
@@ -142,9 +146,14 @@ def preprocess_audio(file_path: str, params: Dict, output_directory: str, mode: 
     _last.rec = None
     stages = N.STAGE_ALL if d.distance >= 1 else N.STAGE_ENVELOPE     # distance < 1 raises in the later calls
     det = default_detector(device)
+
+    def run(st):
+        if save_debug_file:
+            return det.run_host_y16([audio], sample_rate, params, mode=mode, stages=st, resolve_ties=True)[0]
+        return det.run_host([audio], sample_rate, params, mode=mode, stages=st, resolve_ties=True)[0]
+
     try:
-        r = det.run_host([audio], sample_rate, params, mode=mode, stages=stages, want_y=bool(save_debug_file),
-                         resolve_ties=True)[0]
+        r = run(stages)
     except N.BpmxError as exc:
         if stages == N.STAGE_ENVELOPE or not exc.per_file:
             raise
@@ -152,12 +161,9 @@ def preprocess_audio(file_path: str, params: Dict, output_directory: str, mode: 
         # envelope alone now, so the error surfaces from the floor call as in
         # the reference (:1732), after the debug WAV is written
         stages = N.STAGE_ENVELOPE
-        r = det.run_host([audio], sample_rate, params, mode=mode, stages=stages, want_y=bool(save_debug_file),
-                         resolve_ties=True)[0]
+        r = run(stages)
     if save_debug_file:
-        _write_debug_wav(f"{os.path.splitext(file_path)[0]}_filtered_debug.wav", d.sr, r["y"])
-        base = os.path.basename(os.path.splitext(file_path)[0])
-        _write_debug_wav(os.path.join(output_directory, f"{base}_filtered_debug.wav"), d.sr, r["y"])
+        _write_debug_wavs(file_path, output_directory, d.sr, r["y16"])
     env = np.array(r["env"])
     if stages == N.STAGE_ALL:
         _last.rec = {"env": env.copy(), "floor_key": _floor_key(params, d.sr), "peak_key": _peak_key(params, d.sr),
@@ -269,8 +275,8 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
         try:
             if d.distance < 1:
                 raise ValueError(DISTANCE_MSG)
-            res = det.run_host([audio[k][1] for k in idx], fs, params, mode=mode, stages=N.STAGE_ALL, want_y=save,
-                               resolve_ties=True)
+            run = det.run_host_y16 if save else det.run_host      # the debug WAV's int16 samples, not y as f64
+            res = run([audio[k][1] for k in idx], fs, params, mode=mode, stages=N.STAGE_ALL, resolve_ties=True)
         except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
@@ -284,10 +290,7 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
                 out[k] = {"error": err}
                 continue
             if save:
-                path = file_paths[k]
-                _write_debug_wav(f"{os.path.splitext(path)[0]}_filtered_debug.wav", d.sr, r["y"])
-                base = os.path.basename(os.path.splitext(path)[0])
-                _write_debug_wav(os.path.join(output_directory, f"{base}_filtered_debug.wav"), d.sr, r["y"])
+                _write_debug_wavs(file_paths[k], output_directory, d.sr, r["y16"])
             out[k] = {key: r[key] for key in ("env", "floor", "troughs", "peaks", "sr", "flags")}
     return out
 

@@ -88,6 +88,104 @@ class Result:
         return out
 
 
+def peak_capacity(nd: int, distance: int) -> int:
+    """Most peaks ``find_peaks(distance=d)`` can keep in ``nd`` samples: kept
+    peaks are pairwise at least ``distance`` apart (and sanitised troughs are a
+    subset of such a set), so (nd - 1) // distance + 1.  Summed over a batch it
+    sizes the packed tables with no device round trip."""
+    nd, distance = int(nd), max(int(distance), 1)
+    return (nd - 1) // distance + 1 if nd >= 1 else 0
+
+
+@dataclass
+class Packed:
+    """bpmx_pack's outputs for one batch (device tensors): the raw peaks and
+    troughs of every recording as two ragged tables (index, envelope and floor
+    at that index; recording f's entries are ``[off[f], off[f + 1])``), the
+    per-file counters of the run, and optionally the debug WAV's int16
+    samples.  What ``to_host`` downloads is a few MB where ``Result.to_host``
+    moves four sum(Nd)-long 8-byte arrays."""
+    det: "object"
+    sr: int
+    doff: np.ndarray               # host int64 [F+1] decimated offsets
+    cap_peaks: int
+    cap_troughs: int
+    safe_peaks: int                # sum of peak_capacity over the files: a run's totals never exceed it
+    safe_troughs: int
+    pk_off: "object"
+    tr_off: "object"
+    pk_idx: "object"
+    pk_env: "object"
+    pk_floor: "object"
+    tr_idx: "object"
+    tr_env: "object"
+    y16: "object"
+    y_max: "object"
+    n_raw_troughs: "object" = None
+    flags: "object" = None
+
+    @property
+    def n_files(self) -> int:
+        return len(self.doff) - 1
+
+    def _check(self, tp: int, tt: int) -> None:
+        if tp > self.cap_peaks or tt > self.cap_troughs:
+            raise N.BpmxError(f"packed tables too small: {tp} peaks (capacity {self.cap_peaks}), "
+                              f"{tt} troughs (capacity {self.cap_troughs})", N.E_LIMIT)
+
+    def to_host(self) -> List[dict]:
+        """Per-file dicts: sr, n_env, peaks, env_pk, floor_pk, troughs, env_tr,
+        n_raw_troughs, flags (and y16, y_max when packed).  Two rounds of
+        asynchronous copies into pinned staging on the current stream, each
+        ended by one stream synchronise: the per-file offsets and counters
+        first, then the used prefix of each table (and y16), whose length
+        only the offsets tell.  Raises BpmxError (E_LIMIT) when a table's
+        total exceeds its capacity."""
+        torch = _torch()
+        det, F = self.det, self.n_files
+        with det.lock:
+            st = torch.cuda.current_stream(det.device)
+            small = {"pk_off": self.pk_off, "tr_off": self.tr_off, "flags": self.flags,
+                     "n_raw_troughs": self.n_raw_troughs, "y_max": self.y_max}
+            pin = {k: det.staging(k, t.numel(), t.dtype) for k, t in small.items() if t is not None}
+            for k, h in pin.items():
+                h.copy_(small[k], non_blocking=True)
+            st.synchronize()
+            meta = {k: h.numpy().copy() for k, h in pin.items()}
+            pko, tro = meta["pk_off"], meta["tr_off"]
+            tp, tt, tot = int(pko[F]), int(tro[F]), int(self.doff[F])
+            self._check(tp, tt)
+            big = {"pk_idx": (self.pk_idx, tp), "pk_env": (self.pk_env, tp), "pk_floor": (self.pk_floor, tp),
+                   "tr_idx": (self.tr_idx, tt), "tr_env": (self.tr_env, tt)}
+            if self.y16 is not None:
+                big["y16"] = (self.y16, tot)
+            pin = {k: det.staging(k, n, t.dtype) for k, (t, n) in big.items() if n > 0}
+            for k, h in pin.items():
+                h.copy_(big[k][0][:big[k][1]], non_blocking=True)
+            st.synchronize()
+            tab = {k: (pin[k].numpy().copy() if k in pin else np.zeros(0, _NP_OF[str(t.dtype)]))
+                   for k, (t, n) in big.items()}
+        flags = meta["flags"] if "flags" in meta else np.zeros(F, np.int32)
+        nraw = meta["n_raw_troughs"] if "n_raw_troughs" in meta else np.zeros(F, np.int32)
+        pki, tri = tab["pk_idx"].astype(np.int64), tab["tr_idx"].astype(np.int64)
+        out = []
+        for f in range(F):
+            a, b = int(self.doff[f]), int(self.doff[f + 1])
+            p0, p1, t0, t1 = int(pko[f]), int(pko[f + 1]), int(tro[f]), int(tro[f + 1])
+            if flags[f] & N.F_TOO_SHORT:
+                b, p1, t1 = a, p0, t0           # no outputs (include/bpmx.h): empty slices
+            r = dict(sr=self.sr, n_env=b - a, peaks=pki[p0:p1], env_pk=tab["pk_env"][p0:p1],
+                     floor_pk=tab["pk_floor"][p0:p1], troughs=tri[t0:t1], env_tr=tab["tr_env"][t0:t1],
+                     n_raw_troughs=int(nraw[f]), flags=int(flags[f]))
+            if self.y16 is not None:
+                r["y16"], r["y_max"] = tab["y16"][a:b], float(meta["y_max"][f])
+            out.append(r)
+        return out
+
+
+_NP_OF = {"torch.int16": np.int16, "torch.int32": np.int32, "torch.int64": np.int64, "torch.float64": np.float64}
+
+
 class Detector:
     """One libbpmx context on one GPU.
 
@@ -112,6 +210,7 @@ class Detector:
         self.ctx = ctx
         self.lock = threading.RLock()
         self._stream = None
+        self._pinned = {}
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -402,6 +501,170 @@ class Detector:
             out = res.to_host()          # .cpu() waits for this stream only
             self.host_stream().synchronize()
         return out
+
+    def staging(self, name: str, n: int, dtype):
+        """A pinned host tensor of `n` elements for the packed download (one
+        grow-only buffer per name: pinning is far dearer than the copies)."""
+        torch = _torch()
+        t = self._pinned.get(name)
+        if t is None or t.numel() < n or t.dtype != dtype:
+            t = self._pinned[name] = torch.empty(max(n + n // 8, 16), dtype=dtype, pin_memory=True)
+        return t[:n]
+
+    def alloc_packed(self, res: Result, distance: int, want_y16: bool = False, cap_peaks: Optional[int] = None,
+                     cap_troughs: Optional[int] = None) -> Packed:
+        """Device tensors for ``pack``; the default capacities are the sum of
+        ``peak_capacity`` over the files, which a run's totals cannot exceed."""
+        torch = _torch()
+        nd = np.diff(res.doff)
+        safe = int(sum(peak_capacity(n, distance) for n in nd))
+        cp = safe if cap_peaks is None else int(cap_peaks)
+        ct = safe if cap_troughs is None else int(cap_troughs)
+        F, tot, dev = res.n_files, int(res.doff[-1]), self.device
+        e = lambda n, dt: torch.empty(max(int(n), 1), dtype=dt, device=dev)
+        return Packed(det=self, sr=res.sr, doff=res.doff, cap_peaks=cp, cap_troughs=ct, safe_peaks=safe,
+                      safe_troughs=safe, pk_off=e(F + 1, torch.int64), tr_off=e(F + 1, torch.int64),
+                      pk_idx=e(cp, torch.int32), pk_env=e(cp, torch.float64), pk_floor=e(cp, torch.float64),
+                      tr_idx=e(ct, torch.int32), tr_env=e(ct, torch.float64),
+                      y16=e(tot, torch.int16) if want_y16 else None,
+                      y_max=e(F, torch.float64) if want_y16 else None)
+
+    def pack(self, res: Result, distance: int, want_y16: bool = False, out: Optional[Packed] = None) -> Packed:
+        """bpmx_pack on the current stream, behind the run (and any
+        ``resolve_ties``) that filled `res`: the per-peak / per-trough tables
+        and, with `want_y16` (``res.y`` required), the int16 debug samples.
+        Asynchronous with the default capacities.  Tables smaller than those
+        (an `out` from ``alloc_packed`` with its own capacities) are checked
+        here, which waits for the stream: BpmxError (E_LIMIT) when a total
+        exceeds its capacity; the offsets then still hold the true totals and
+        nothing at or beyond the capacity was written."""
+        if res.peaks is None or res.troughs is None or res.floor is None:
+            raise N.BpmxError("pack needs a Result with floor, troughs and peaks", N.E_ARG)
+        if out is None:
+            out = self.alloc_packed(res, distance, want_y16=want_y16)
+        if want_y16 and (res.y is None or out.y16 is None):
+            raise N.BpmxError("want_y16 needs a Result that holds y (want_y=True)", N.E_ARG)
+        out.n_raw_troughs, out.flags = res.n_raw_troughs, res.flags
+        ptr = lambda t: None if t is None else t.data_ptr()
+        o = N.Out()
+        o.env, o.floor, o.y = ptr(res.env), ptr(res.floor), ptr(res.y)
+        o.troughs, o.peaks = ptr(res.troughs), ptr(res.peaks)
+        o.n_troughs, o.n_peaks, o.flags = ptr(res.n_troughs), ptr(res.n_peaks), ptr(res.flags)
+        o.n_raw_troughs = ptr(res.n_raw_troughs)
+        k = N.PackedOut()
+        k.cap_peaks, k.cap_troughs = out.cap_peaks, out.cap_troughs
+        k.pk_off, k.tr_off = ptr(out.pk_off), ptr(out.tr_off)
+        k.pk_idx, k.pk_env, k.pk_floor = ptr(out.pk_idx), ptr(out.pk_env), ptr(out.pk_floor)
+        k.tr_idx, k.tr_env = ptr(out.tr_idx), ptr(out.tr_env)
+        if want_y16:
+            k.y16, k.y_max = ptr(out.y16), ptr(out.y_max)
+        fo = res.frame_offsets
+        with self.lock:
+            N.check(self.L.bpmx_pack(self.ctx, res.n_files, fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                     res.ds, ctypes.byref(o), ctypes.byref(k), self.stream_handle()), "bpmx_pack")
+        if out.cap_peaks < out.safe_peaks or out.cap_troughs < out.safe_troughs:
+            F = res.n_files
+            out._check(int(out.pk_off[F].item()), int(out.tr_off[F].item()))
+        return out
+
+    def _batch_on_device(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str, stages: int,
+                         want_y: bool, resolve_ties: bool, options: int = 0):
+        """Upload one batch, run it and re-decide its ties (the caller holds the
+        lock and has the host stream current) -> (Result, Design)."""
+        torch = _torch()
+        dt = recordings[0].dtype
+        ch = 1 if recordings[0].ndim == 1 else recordings[0].shape[1]
+        for r in recordings:
+            if r.dtype != dt or (1 if r.ndim == 1 else r.shape[1]) != ch:
+                raise ValueError("a batch needs one sample format and channel count")
+        fo = np.zeros(len(recordings) + 1, dtype=np.int64)
+        fo[1:] = np.cumsum([r.shape[0] for r in recordings])
+        host = np.concatenate([np.ascontiguousarray(r).reshape(-1) for r in recordings])
+        d = design(fs, params, log=False)
+        pcm = torch.from_numpy(host).to(self.device)
+        res = self.run(pcm, fo, fs, params, mode=mode, stages=stages, channels=ch, want_y=want_y, d=d,
+                       options=options)
+        if resolve_ties:
+            self.resolve_ties(res, params, stages, options)
+        return res, d
+
+    def _in_callers_order(self, fn, recordings: List[np.ndarray], longest_first: bool) -> List[dict]:
+        """`fn(recordings)` with a ragged batch handed over longest first
+        (``run_host``'s rule), results back in the caller's order."""
+        if not (longest_first and len({r.shape[0] for r in recordings}) > 1):
+            return fn(recordings)
+        from .shard import longest_first as _lf
+        perm = _lf([r.shape[0] for r in recordings])
+        res = fn([recordings[i] for i in perm])
+        out: List[dict] = [None] * len(recordings)
+        for k, i in enumerate(perm):
+            out[i] = res[k]
+        return out
+
+    def run_host_packed(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
+                        stages: int = N.STAGE_ALL, resolve_ties: bool = False, want_y16: bool = False,
+                        longest_first: bool = True) -> List[dict]:
+        """``run_host`` for consumers that read the envelope and the floor only
+        at the raw peaks and troughs (the native beat stages, the result
+        gather): upload, run, ``resolve_ties``, ``pack`` and the packed
+        download (``Packed.to_host``'s per-file dicts).  env, floor, y and the
+        sum(Nd)-long index arrays never leave the device.  Same lock, stream
+        and longest-first rules as ``run_host``."""
+        torch = _torch()
+        if not recordings:
+            return []
+
+        def go(recs):
+            with self.lock, torch.cuda.stream(self.host_stream()):
+                res, d = self._batch_on_device(recs, fs, params, mode, stages, want_y16, resolve_ties)
+                out = self.pack(res, d.distance, want_y16=want_y16).to_host()
+                self.host_stream().synchronize()
+            return out
+
+        return self._in_callers_order(go, list(recordings), longest_first)
+
+    def run_host_y16(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
+                     stages: int = N.STAGE_ALL, resolve_ties: bool = False, longest_first: bool = True) -> List[dict]:
+        """``run_host``'s per-file dicts (whole env, floor, troughs, peaks) with
+        the debug WAV's samples quantised on the device: ``y16`` (int16) and
+        ``y_max`` per file, ``y`` None.  The filtered signal is made in HBM
+        and read there; 2 bytes per sample come back instead of 8."""
+        torch = _torch()
+        if not recordings:
+            return []
+
+        def go(recs):
+            with self.lock, torch.cuda.stream(self.host_stream()):
+                res, d = self._batch_on_device(recs, fs, params, mode, stages, True, resolve_ties)
+                tot = int(res.doff[-1])
+                d16 = torch.empty(max(tot, 1), dtype=torch.int16, device=self.device)
+                dmx = torch.empty(res.n_files, dtype=torch.float64, device=self.device)
+                self._pack_y16(res, d16, dmx)
+                h16 = self.staging("y16", tot, d16.dtype)
+                hmx = self.staging("y_max", res.n_files, dmx.dtype)
+                h16.copy_(d16[:tot], non_blocking=True)
+                hmx.copy_(dmx, non_blocking=True)
+                res.y = None                     # stays on the device
+                out = res.to_host()              # .cpu() waits for this stream, so the two copies above are done
+                self.host_stream().synchronize()
+                y16, ymax = h16.numpy().copy(), hmx.numpy().copy()
+            for f, r in enumerate(out):
+                a = int(res.doff[f])
+                r["y16"], r["y_max"] = y16[a:a + len(r["env"])], float(ymax[f])
+            return out
+
+        return self._in_callers_order(go, list(recordings), longest_first)
+
+    def _pack_y16(self, res: Result, y16, y_max) -> None:
+        """bpmx_pack for the int16 debug samples alone (no tables)."""
+        o = N.Out()
+        o.y = res.y.data_ptr()
+        k = N.PackedOut()
+        k.y16, k.y_max = y16.data_ptr(), y_max.data_ptr()
+        fo = res.frame_offsets
+        with self.lock:
+            N.check(self.L.bpmx_pack(self.ctx, res.n_files, fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                     res.ds, ctypes.byref(o), ctypes.byref(k), self.stream_handle()), "bpmx_pack")
 
     def run_env_host(self, envs: List[np.ndarray], sr: int, params: dict, stages: int,
                      floors: Optional[List[np.ndarray]] = None, options: int = 0,

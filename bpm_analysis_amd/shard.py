@@ -71,9 +71,11 @@ def _load(it, fs):
     return fs, np.asarray(it)
 
 
-def _detect_local(items, idx, fs, params, mode, detector):
+def _detect_local(items, idx, fs, params, mode, detector, packed=False):
     """The hot path over this rank's recordings: one ragged batch per (rate,
-    sample format, channels), as dropin.analyze_wav_files groups them."""
+    sample format, channels), as dropin.analyze_wav_files groups them.
+    `packed`: the detector's packed download (``run_host_packed``: per-peak
+    tables instead of whole envelopes)."""
     from . import _native as N
     from .design import design
     from .dropin import DISTANCE_MSG, PADLEN_MSG, _file_error
@@ -94,8 +96,8 @@ def _detect_local(items, idx, fs, params, mode, detector):
             d = design(f, params, log=False)
             if d.distance < 1:
                 raise ValueError(DISTANCE_MSG)
-            out = detector.run_host([data[i][1] for i in ids], f, params, mode=mode, stages=N.STAGE_ALL,
-                                    resolve_ties=True)
+            run = detector.run_host_packed if packed else detector.run_host
+            out = run([data[i][1] for i in ids], f, params, mode=mode, stages=N.STAGE_ALL, resolve_ties=True)
         except (ValueError, N.BpmxError) as exc:
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                   # HIP / device failure: the rank fails, not the files
@@ -121,7 +123,8 @@ def _pad_rows(rows: List[np.ndarray], width: int, fill, dtype) -> np.ndarray:
 
 def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: str = "native",
                 start_bpm_hint: Optional[float] = None, beats="native", detector=None,
-                group=None, host_threads: int = 0, chunk_frames: int = 1 << 30) -> Optional[List[dict]]:
+                group=None, host_threads: int = 0, chunk_frames: int = 1 << 30,
+                packed: bool = True) -> Optional[List[dict]]:
     """A ragged batch of independent recordings over the ranks of a
     torch.distributed process group (one process per GPU); the
     per-file loop it replaces is gui.py:202-251.
@@ -136,6 +139,12 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
       ``host_threads`` host threads while the GPU runs the next chunk
       (``beats="native"``: libbpmx_host.so, beats.analyze_fast;
       ``"python"``: beats.analyze_recording; False: raw peaks only).
+      The records below need the raw peaks, the beats and the curve only, and
+      the native beat stage reads env and floor at the raw peaks alone, so
+      with ``beats`` "native" or False and a detector that offers
+      ``run_host_packed`` the GPU results come back packed (per-peak tables,
+      engine.Packed) and ``_host.beats_packed`` takes them; ``"python"``
+      needs whole envelopes and keeps ``run_host``, as does ``packed=False``.
     * Result gather to rank 0 (RCCL under the "nccl" backend, gloo on CPU):
       one int64 slab [files, 4 + raw peaks + final beats] and one f64 slab
       [files, 2 x BPM-curve points] per rank, padded to the widest over all
@@ -190,13 +199,17 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
                 out.append(FileResult.from_analysis(i, pk, int(r["flags"]), a))
                 continue
             from . import _host
-            a = _host.beats(r["env"], r["sr"], r["floor"], pk, bparams, start_bpm_hint)
+            if "env_pk" in r:
+                a = _host.beats_packed(pk, r["env_pk"], r["floor_pk"], r["n_env"], r["sr"], bparams, start_bpm_hint)
+            else:
+                a = _host.beats(r["env"], r["sr"], r["floor"], pk, bparams, start_bpm_hint)
             if "error" in a:
                 out.append(FileResult(i, error=a["error"]))
             else:
                 out.append(FileResult(i, pk, a["final_peaks"], a["bpm_times"], a["bpm"], int(r["flags"])))
         return out
 
+    use_packed = bool(packed) and beats != "python" and hasattr(detector, "run_host_packed")
     bparams = None
     if beats and beats != "python":
         from . import _host
@@ -206,7 +219,7 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
     with ThreadPoolExecutor(host_threads) as ex:
         futs = []
         for idx in chunks:                             # the GPU runs chunk k+1 while host threads take chunk k
-            det_res = _detect_local(items, idx, fs, params, mode, detector)
+            det_res = _detect_local(items, idx, fs, params, mode, detector, use_packed)
             per = max(1, len(idx) // host_threads)
             futs += [ex.submit(host_stage, idx[a:a + per], det_res) for a in range(0, len(idx), per)]
         for fu in futs:

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BPMX_ABI_VERSION 2
+#define BPMX_ABI_VERSION 3
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
 enum bpmx_dtype { BPMX_DT_U8 = 0, BPMX_DT_I16 = 1, BPMX_DT_I32 = 2, BPMX_DT_F32 = 3, BPMX_DT_F64 = 4 };
@@ -229,6 +229,49 @@ typedef struct {
  * NULL = bpmx_run.  Never pipelined. */
 int bpmx_run_ordered(bpmx_ctx *ctx, const bpmx_params *params, const bpmx_batch *batch, const bpmx_out *out,
                      const bpmx_peak_order *order, void *stream);
+
+/* Compact results, packed on the device (bpmx_pack).
+ *
+ * A finished run leaves env, floor, troughs and peaks as sum(Nd)-long 8-byte
+ * arrays, but the stages after it read env and floor only at the raw peaks
+ * and the troughs (a few hundred positions per minute of recording).  These
+ * tables hold exactly that, ragged, file after file:
+ *
+ *   pk_off[f]  = sum_{g<f} n_peaks[g]    (pk_off[n_files] = the total)
+ *   for k < n_peaks[f], i = peaks[D_f + k], j = pk_off[f] + k:
+ *     pk_idx[j] = i,  pk_env[j] = env[D_f + i],  pk_floor[j] = floor[D_f + i]
+ *
+ * and the same from troughs / n_troughs into tr_off, tr_idx, tr_env.  Values
+ * are copied bit for bit.  The offsets always hold the true totals; an entry
+ * whose table position j is >= the table's capacity is not written, so a
+ * caller detects an overflow from off[n_files] > cap.  Each table is optional:
+ * it is built when its offsets pointer is set (its other pointers are then
+ * required, with in->peaks / in->troughs, the matching count and in->env, and
+ * in->floor for the peak table).
+ *
+ * y16 (optional; needs in->y and y_max): the debug WAV's samples
+ * (bpm_analysis.py:1057-1060, np.int16(y / np.max(np.abs(y)) * 32767)).  Per
+ * file, m = max|y| over its slice (the largest |y| bit pattern, so a NaN wins),
+ * y_max[f] = m, and y16[D_f + i] = (int16_t)trunc((y[D_f + i] / m) * 32767.0),
+ * the division and the multiplication rounded separately; a file whose m is
+ * 0, NaN or inf gets zeros.  y16 needs 2-byte alignment only. */
+typedef struct {
+    int64_t cap_peaks, cap_troughs; /* table capacities, entries */
+    int64_t *pk_off, *tr_off;       /* device [n_files + 1] */
+    int32_t *pk_idx;                /* device [cap_peaks] */
+    double *pk_env, *pk_floor;      /* device [cap_peaks] */
+    int32_t *tr_idx;                /* device [cap_troughs] */
+    double *tr_env;                 /* device [cap_troughs] */
+    int16_t *y16;                   /* optional device [sum(Nd)] */
+    double *y_max;                  /* device [n_files] (with y16) */
+} bpmx_packed;
+
+/* Pack the outputs `in` of a finished bpmx_run / bpmx_run_ordered over the
+ * batch geometry (n_files, host frame_offsets, ds: the D_f of bpmx_out) into
+ * `out`, asynchronously on `stream` (the run's stream, or one ordered after
+ * it).  No host synchronisation; scratch comes from ctx. */
+int bpmx_pack(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, const bpmx_out *in,
+              const bpmx_packed *out, void *stream);
 
 /* Synthetic int16 recordings straight into HBM: file f gets seed seed0+f,
  * frames [frame_offsets[f], frame_offsets[f+1]) of pcm (device). */
