@@ -77,32 +77,14 @@ struct QuantArgs {
     int32_t slot[Q_SLOTS];  /* bitmask of the qv slots level l fills */
     double q[Q_SLOTS];
     double *qv;             /* [F][Q_SLOTS] */
-    int64_t skip_le;        /* k_ql_*: files with n <= skip_le are done by k_quantile_reg */
+    int64_t skip_le;        /* k_qv_*: files with n <= skip_le are done by k_quantile_reg */
     const int32_t *skip;    /* [F] optional: skip files with skip[f] != 0 (the lazy static-floor level) */
     int32_t stats;          /* k_quantile_reg: also write the block max/min tables */
 };
 
-/* k_quantile for long recordings over many workgroups (k_detect.hip):
- * MSD radix select with 11-bit digits (6 passes over the 64-bit keys), each
- * pass a histogram of every chunk of the recording (all levels at once) into
- * global bins, then a select step per (recording, level) */
-constexpr int QL_BITS = 11, QL_BINS = 1 << QL_BITS, QL_PASSES = 6, QL_CHUNK = 32768;
-struct QlState {
-    unsigned long long prefix, mask;
-    long long r;            /* rank still to find inside the selected bin */
-    long long lo;           /* the order statistic's rank (floor((n-1) q)) */
-    unsigned long long next; /* min key above the answer (atomicMin), for the interpolation */
-    int32_t top, eq;        /* top: q (n-1) >= n-1; eq: another key equals the answer */
-};
-struct QlArgs {
-    QuantArgs Q;
-    QlState *st;            /* [F][Q_SLOTS] */
-    unsigned int *hist;     /* [QL_PASSES][F][Q_SLOTS][QL_BINS] (zeroed before pass 0) */
-    int32_t pass;
-};
-/* The same quantiles in five launches and two passes over env (k_detect.hip,
- * r06): bins of the order-preserving key over the recording's own key range
- * (k_qv_range, from the block max/min tables), one histogram for all levels
+/* k_quantile for long recordings over many workgroups, in five launches and
+ * two passes over env (k_detect.hip): bins of the order-preserving key over
+ * the recording's own key range (k_qv_range, from the block max/min tables), one histogram for all levels
  * (k_qv_hist), the target bin and the rank inside it per level (k_qv_select),
  * the target bin's keys gathered per level plus the least key above it
  * (k_qv_collect), the exact order statistics among the gathered keys by a
@@ -133,11 +115,6 @@ __global__ void k_qv_hist(QvArgs A);
 __global__ void k_qv_select(QvArgs A);
 __global__ void k_qv_collect(QvArgs A);
 __global__ void k_qv_final(QvArgs A);
-__global__ void k_ql_init(QlArgs A);
-__global__ void k_ql_hist(QlArgs A);
-__global__ void k_ql_select(QlArgs A);
-__global__ void k_ql_next(QlArgs A);
-__global__ void k_ql_final(QlArgs A);
 
 struct BlockStatArgs {
     const double *env;

@@ -7,12 +7,11 @@
 #include <vector>
 
 #include "bpmx_ctx.h"
+#include "bpmx_run.h"
 #include "bpmx_kernels.h"
 
 namespace bpmx {
-int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O, hipStream_t s,
-                    int F, const std::vector<int64_t> &foff, const std::vector<int64_t> &doff, int64_t maxnd,
-                    const int64_t *d_foff, const int64_t *d_doff, const int32_t *d_active,
+int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O, const RunGeo &G,
                     const QuantArgs *qa = nullptr,    /* non-null: the fused Hilbert kernel also fills qa->qv */
                     const InitOutArgs *io = nullptr); /* non-null: k_native_carry resets the run's outputs */
 /* k_bluestein.hip: hb = N * Hilbert transform of yd for the listed recordings */

@@ -1,0 +1,190 @@
+/*
+ * bpmx_plan.h — which kernels a run takes and how they are sized, as pure host
+ * arithmetic over the run's parameters and the batch's shape: no HIP runtime
+ * call, no context, no allocation.  bpmx_run.hip sequences the launches over
+ * these plans; tests/plan_driver.hip prints them without a GPU.
+ */
+#ifndef BPMX_PLAN_H
+#define BPMX_PLAN_H
+
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+
+#include "bpmx_kernels.h"
+
+namespace bpmx {
+
+/* the sorted-union rolling-quantile kernel that serves need_merge */
+enum { RQ_UNION_16 = 0, RQ_UNION_32 = 1, RQ_UNION_G = 2 };   /* <RQ_T,16>, <RQ_T,32>, k_rolling_quantile_g */
+
+/* dynamic LDS the global-union kernel may ask for */
+constexpr size_t RQ_G_LDS_MAX = 160 * 1024;
+
+/* FLOOR and PEAKS: every path decision and launch geometry of a run */
+struct DetectPlan {
+    bool do_floor, do_peaks;
+    /* noise window < min_periods: pandas' rolling() raises ValueError, but only
+     * for recordings that reach it (>= 5 troughs, :1073-1085); those get
+     * BPMX_F_BAD_WINDOW and the rest of the batch runs normally */
+    bool bad_window;
+    /* find_peaks: k_find_peaks_lds for every recording it holds; the others
+     * (longer than FPL_NMIN, or more than FL_MC maxima) take the multi-
+     * workgroup k_fpl_* path when the batch has long recordings, else the
+     * one-workgroup k_find_peaks (BPMX_OPT_PEAKS_GLOBAL, or an ordered run,
+     * whose candidate export and visiting ranks k_find_peaks implements:
+     * k_find_peaks for all) */
+    bool long_files;            /* some recording is beyond k_quantile_reg */
+    bool fp_global, fp_long;
+    int32_t fp_nu;              /* k_fpl_*: scan units per recording */
+    dim3 g_unit, g_prom, g_dch;
+    unsigned bs_gy;             /* k_block_stats: a few workgroups per long recording when the batch is small */
+    /* the draft bracket (k_draft_bounds, k_draft_points) unless BPMX_OPT_DRAFT_FULL */
+    bool bounds;
+    unsigned db_gy, dp_gy;
+    /* recordings of <= WM_MMAX samples: everything after the draft bracket
+     * in one launch (k_floor_wm), the static floor's quantile included */
+    bool floor_wm;
+    /* rolling-quantile geometry: T outputs per step, sorted union in LDS */
+    int64_t W;
+    int cap;
+    size_t lds;
+    /* wavelet-matrix kernel for recordings that fit its LDS budget; the
+     * sorted-union kernel for longer ones (or when forced) */
+    bool use_wm, need_merge;
+    /* windows beyond the LDS sorted-union kernel: the same algorithm with
+     * the union in global scratch (any window, any length) */
+    bool merge_g;
+    int64_t gcap;
+    size_t lds_g;
+    int64_t wm_n;
+    size_t wm_lds_p, wm_lds;    /* pruned and unpruned layouts */
+    /* long recordings: the pruned wavelet matrix over chunks of wm_c outputs
+     * (a chunk's windows reach wm_c + W - 1 samples); a recording with a
+     * chunk it cannot take falls to the sorted-union kernel */
+    int64_t wm_c, wm_nch;
+    bool wm_chunks;
+    /* the union kernels (need_merge): outputs per workgroup, chunks per recording, which kernel */
+    int64_t chunk, nch;
+    int rq_union;
+    /* k_interp / k_floor_final stride over a recording with gx workgroups:
+     * 8, or more when the batch has few recordings */
+    dim3 g2, gi, gf;
+    char err[96];               /* the message that goes with BPMX_E_LIMIT */
+};
+
+inline int too_long(DetectPlan &D) {
+    std::snprintf(D.err, sizeof D.err, "recording too long for the chunked rolling quantile");
+    return BPMX_E_LIMIT;
+}
+
+inline int detect_plan(const bpmx_params &P, int F, int64_t maxnd, bool ordered, DetectPlan *out) {
+    DetectPlan &D = *out;
+    D = DetectPlan{};
+    D.do_floor = P.stages & BPMX_STAGE_FLOOR;
+    D.do_peaks = P.stages & BPMX_STAGE_PEAKS;
+    D.bad_window = D.do_floor && P.noise_window < P.min_periods;
+    D.bounds = D.do_floor && !(P.options & BPMX_OPT_DRAFT_FULL);
+
+    D.long_files = maxnd > QR_MAX;
+    D.fp_global = (P.options & BPMX_OPT_PEAKS_GLOBAL) != 0 || ordered;
+    D.fp_long = !D.fp_global && maxnd > FPL_NMIN;
+    D.fp_nu = (int32_t)((maxnd - 2 + FPL_U - 1) / FPL_U);
+    D.g_unit = dim3((unsigned)((((maxnd - 2 + FPL_U - 1) / FPL_U) + 3) / 4), (unsigned)F);
+    D.g_prom = dim3((unsigned)((maxnd / 2 + 1 + 255) / 256), (unsigned)F);
+    D.g_dch = dim3((unsigned)((maxnd / 2 + 1 + FPC_S - 1) / FPC_S), (unsigned)F);
+    D.bs_gy = (unsigned)std::min<int64_t>((((maxnd + 63) >> 6) + 3) / 4, std::max<int64_t>(1, 2048 / F));
+    if (!D.do_floor) return BPMX_OK;
+
+    D.floor_wm = !(P.options & (BPMX_OPT_ROLLQ_MERGE | BPMX_OPT_ROLLQ_GLOBAL | BPMX_OPT_ROLLQ_NOPRUNE)) &&
+                 maxnd <= WM_MMAX;
+    const int64_t W = D.bad_window ? P.min_periods : P.noise_window;
+    D.W = W;
+    D.cap = (int)((W + RQ_T - 1 + 63) / 64 * 64);
+    D.lds = rollq_lds_bytes(RQ_T, D.cap);
+    D.use_wm = !(P.options & (BPMX_OPT_ROLLQ_MERGE | BPMX_OPT_ROLLQ_GLOBAL));
+    D.need_merge = !D.use_wm || maxnd > WM_MMAX;
+    D.merge_g = D.need_merge && (D.cap > 32 * RQ_T || W + RQ_T >= 65000 || (P.options & BPMX_OPT_ROLLQ_GLOBAL));
+    D.gcap = (std::min<int64_t>(W + RQ_T, maxnd + 64) + 63) / 64 * 64;
+    D.lds_g = rollq_g_lds_bytes(RQ_T, D.gcap);
+    if (D.merge_g && D.lds_g > RQ_G_LDS_MAX) {
+        std::snprintf(D.err, sizeof D.err, "noise window and recording both longer than %d samples",
+                      (160 * 1024 - 16384) / 4 * 64);
+        return BPMX_E_LIMIT;
+    }
+    D.wm_n = std::min<int64_t>(maxnd, WM_MMAX);
+    D.wm_lds_p = wm_layout(D.wm_n, true).total;
+    D.wm_lds = wm_layout(D.wm_n, false).total;
+    D.wm_c = (WM_MMAX - W + 1) / 64 * 64;
+    D.wm_chunks = D.use_wm && maxnd > WM_MMAX && !(P.options & BPMX_OPT_ROLLQ_NOPRUNE) && D.wm_c >= 2048;
+    D.wm_nch = D.wm_chunks ? (maxnd + D.wm_c - 1) / D.wm_c : 1;
+    if (D.wm_nch > 65535) return too_long(D);
+    D.g2 = dim3((unsigned)std::min<int64_t>((maxnd + 255) / 256, std::max<int64_t>(8, 2048 / F)), F);
+    /* with no long recording only those with > WM_TRMAX troughs (rare): two workgroups each */
+    D.gi = maxnd <= WM_MMAX && D.use_wm ? dim3(2, (unsigned)F) : D.g2;
+    /* one workgroup per recording unless they are long: most recordings
+     * exit at once, and a static or draft floor is a short fill */
+    D.gf = dim3(maxnd > 65536 ? D.g2.x : 1u, (unsigned)F);
+    if (D.need_merge) {
+        /* long recordings: a workgroup per chunk of outputs (each chunk pays
+         * one extra window fill: ~13 merge rounds against 32 or 16 tiles).
+         * 8192 outputs per chunk, halved (down to 1024) while the batch
+         * gives fewer than 1024 workgroups: a chunk's first-window fill is
+         * fixed overhead, worth paying only when CUs would sit idle */
+        D.chunk = 8192;
+        while (D.chunk > 1024 && (int64_t)F * ((maxnd + D.chunk - 1) / D.chunk) < 1024) D.chunk >>= 1;
+        /* the global-union kernel pays a window-sized fill per chunk: chunks of at least W */
+        if (D.merge_g) D.chunk = std::max<int64_t>(D.chunk, (W + RQ_T - 1) / RQ_T * RQ_T);
+        D.nch = (maxnd + D.chunk - 1) / D.chunk;
+        if (D.nch > 65535) return too_long(D);
+        D.rq_union = D.merge_g ? RQ_UNION_G : D.cap <= 16 * RQ_T ? RQ_UNION_16 : RQ_UNION_32;
+    }
+    if (D.bounds) {
+        /* find_peaks' distance spaces the troughs, so a recording has at most Nd / distance + 1 */
+        const int64_t trmax = maxnd / std::max<int64_t>(1, P.distance) + 1;
+        D.db_gy = (unsigned)std::max<int64_t>(1, (trmax + DB_T - 1) / DB_T);
+        /* at most 4 workgroups per recording, each taking every
+         * gridDim.y-th chunk of 32 troughs */
+        D.dp_gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4, (trmax + DP_CHUNK - 1) / DP_CHUNK));
+    }
+    return BPMX_OK;
+}
+
+/* Reference-mode envelope: the forward pass in row chunks while k_ref_pick
+ * gathers the next chunks on a side stream, and (chain mode) the Kahan pass in
+ * row chunks whose means k_ref_env_mean forms on the side stream.  The run
+ * takes the unsplit form when wants_split is 0 or the side stream or its
+ * events cannot be had. */
+struct RefEnvPlan {
+    /* chain mode (the rolling mean's outputs formed in parallel afterwards) */
+    bool chain;
+    int64_t rows;               /* maxnd + 30: the padded signal */
+    /* chunk k: rows [R (2^k - 1), R (2^(k+1) - 1)): the first gather is
+     * short (it is not overlapped), the later ones grow while the
+     * gather (faster per row than the sequential pass) stays ahead */
+    int64_t nfc;
+    int64_t fwd_row(int64_t k) const { return std::min(rows, REF_FWD_ROWS * ((int64_t(1) << k) - 1)); }
+    bool wants_split;           /* nfc >= 2 and not BPMX_OPT_REF_NOSPLIT */
+    /* chain mode of a split run: the Kahan pass in row chunks ending at 1/2,
+     * 3/4, 7/8 and all of the rows (nkc 0: one pass) */
+    int64_t kend[4];
+    int nkc;
+};
+
+inline RefEnvPlan ref_env_plan(int64_t maxnd, int32_t env_window, int32_t options) {
+    RefEnvPlan R{};
+    R.chain = !(options & BPMX_OPT_REF_SERIAL_MEAN) && env_window > 1;
+    R.rows = maxnd + 30;
+    R.nfc = 1;
+    while (R.fwd_row(R.nfc) < R.rows) ++R.nfc;
+    R.wants_split = R.nfc >= 2 && !(options & BPMX_OPT_REF_NOSPLIT);
+    if (R.chain && R.wants_split && maxnd >= 4096) {
+        for (int k = 1; k <= 3; ++k) R.kend[R.nkc++] = (maxnd - (maxnd >> k)) & ~(int64_t)63;
+        R.kend[R.nkc++] = maxnd;
+    }
+    return R;
+}
+
+}  // namespace bpmx
+
+#endif

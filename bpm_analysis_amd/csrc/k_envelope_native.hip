@@ -1928,10 +1928,14 @@ HbTables *hb_tables(bpmx_ctx *ctx, int64_t nd, int window, HilbPlan *P, size_t *
     return &it->second;
 }
 
-int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O, hipStream_t s,
-                    int F, const std::vector<int64_t> &foff, const std::vector<int64_t> &doff, int64_t maxnd,
-                    const int64_t *d_foff, const int64_t *d_doff, const int32_t *d_active, const QuantArgs *qa,
-                    const InitOutArgs *io) {
+int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O, const RunGeo &G,
+                    const QuantArgs *qa, const InitOutArgs *io) {
+    hipStream_t s = G.s;
+    const int F = G.F;
+    const std::vector<int64_t> &foff = G.foff, &doff = G.doff;
+    const int64_t maxnd = G.maxnd;
+    const int64_t *d_foff = G.d_foff, *d_doff = G.d_doff;
+    const int32_t *d_active = G.d_active;
     const int ds = P->ds;
     if (ds > NAT_DSMAX) return fail(BPMX_E_LIMIT, "native mode supports ds <= " + std::to_string(NAT_DSMAX));
     int rc = BPMX_OK;

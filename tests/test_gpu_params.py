@@ -387,10 +387,8 @@ def test_draft_staging_limits(det, w):
 # ----------------------------------------------------------------------------
 # recordings beyond WM_MMAX and FPL_NMIN: the host's kernel selection
 # ----------------------------------------------------------------------------
-# From bpmx_api.hip (rolling-quantile geometry), with RQ_T = 256 and WM_MMAX = 18432:
-#   cap = (W + RQ_T - 1 + 63) / 64 * 64;  cap <= 16 * RQ_T  <=>  W <= 3841   (<RQ_T,16>, else <RQ_T,32>)
-#                                         cap <= 32 * RQ_T  <=>  W <= 7937   (else k_rolling_quantile_g)
-#   wm_c = (WM_MMAX - W + 1) / 64 * 64;   wm_c >= 2048      <=>  W <= 16385  (else no chunked wavelet matrix)
+# The switch points are detect_plan's (csrc/bpmx_plan.h: cap, merge_g, wm_c); tests/test_plan.py
+# reads them off the plan itself at the windows below.
 LONG_N = [WM_MMAX + 64, 20000, 66000]
 LONG_WINDOWS = [3, 151, 3841, 3842, 7937, 7938, 16385, 16386] + [n + 5 for n in LONG_N]
 LONG_DISTANCES = [1, 15, 300]

@@ -1390,7 +1390,7 @@ def test_native_fused_yd_identical(det):
 def test_native_envelope_independent_of_placement(det):
     """A recording's native envelope (and everything after it) is bit-identical
     wherever its PCM lies: a batch started 1..8 frames into an aligned buffer
-    (the library realigns the base, bpmx_api.hip run_impl), and the recording
+    (the library realigns the base, bpmx_run.hip build_geometry), and the recording
     at different positions of a ragged batch."""
     import torch
     from bpm_analysis_amd import _native as N

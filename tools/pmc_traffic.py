@@ -35,7 +35,7 @@ def short_name(kernel: str) -> str:
 
 
 # kernels launched more than once per step under different launch labels
-# (bpmx_api.hip's LAUNCH names), in launch order within a step: their
+# (bpmx_run.hip's LAUNCH names), in launch order within a step: their
 # dispatches are labelled by their position in that cycle
 LABEL_CYCLE = {"k_find_peaks_lds": ["k_find_peaks[troughs]", "k_find_peaks[peaks]"],
                "k_rollq_wm_t": ["k_rollq_wm[draft]"]}      # r05: the floor's other passes are k_floor_wm

@@ -1,5 +1,5 @@
 """Per-stage GPU time from a rocprofv3 run of the library (roctx "bpmx:<stage>"
-ranges, bpmx_api.hip StageRange):
+ranges, bpmx_run.hip StageRange):
 
     rocprofv3 --kernel-trace --marker-trace --hip-runtime-trace --output-format csv -d DIR -o run -- python3 bench.py ...
     python tools/stage_profile.py DIR [--steps K]
