@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # BPMX_LIB: another build of the same library (diagnostic A/B runs of kernel variants)
 LIB_PATH = os.environ.get("BPMX_LIB") or os.path.join(_HERE, "libbpmx.so")
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 DT_U8, DT_I16, DT_I32, DT_F32, DT_F64 = 0, 1, 2, 3, 4
 MODE_REFERENCE, MODE_NATIVE = 0, 1
@@ -36,12 +36,14 @@ OPT_REF_SERIAL_MEAN = 1024
 OPT_STATS = 2048
 OPT_HILBERT_BLUESTEIN = 4096
 OPT_REF_NOSPLIT = 8192
+OPT_BEATS_GLOBAL = 16384           # bpmx_beats_device, through bpmx_set_options (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
+BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS
 
 EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy", "bpmx_decimated_length",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
-           "bpmx_stats", "bpmx_set_pipeline"]
+           "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options"]
 
 
 class Params(ctypes.Structure):
@@ -82,6 +84,14 @@ class PackedOut(ctypes.Structure):
                 ("pk_idx", ctypes.c_void_p), ("pk_env", ctypes.c_void_p), ("pk_floor", ctypes.c_void_p),
                 ("tr_idx", ctypes.c_void_p), ("tr_env", ctypes.c_void_p),
                 ("y16", ctypes.c_void_p), ("y_max", ctypes.c_void_p)]
+
+
+class BeatsOut(ctypes.Structure):
+    """bpmx_beats_out: the device arrays bpmx_beats_device fills (per-file
+    slices at pk_off[f]; pass and tags may be None)."""
+    _fields_ = [("final_idx", ctypes.c_void_p), ("n_final", ctypes.c_void_p), ("bpm_t", ctypes.c_void_p),
+                ("bpm", ctypes.c_void_p), ("n_bpm", ctypes.c_void_p), ("pass_", ctypes.c_void_p),
+                ("tags", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
 class BpmxError(RuntimeError):
@@ -148,6 +158,13 @@ def load() -> ctypes.CDLL:
     L.bpmx_stats.restype = ctypes.c_int
     L.bpmx_set_pipeline.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.bpmx_set_pipeline.restype = ctypes.c_int
+    if hasattr(L, "bpmx_beats_device"):      # an older build fails the ABI check below, not here
+        from ._host import BeatParams
+        L.bpmx_beats_device.argtypes = [P, I32, I32, ctypes.POINTER(BeatParams), ctypes.c_double,
+                                        ctypes.POINTER(PackedOut), P, ctypes.POINTER(BeatsOut), P]
+        L.bpmx_beats_device.restype = ctypes.c_int
+        L.bpmx_set_options.argtypes = [P, I32]
+        L.bpmx_set_options.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

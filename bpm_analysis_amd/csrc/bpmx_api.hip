@@ -1,6 +1,7 @@
 /*
  * bpmx_api.hip — host side of the C ABI (include/bpmx.h): context, scratch,
- * synthetic input, per-kernel event timing, the pipelined run and bpmx_pack.
+ * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack and
+ * bpmx_beats_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include "bpmx_kernels.h"
 #include "bpmx_ctx.h"
 #include "bpmx_run.h"
+#include "bpmx_plan.h"
 #include "bpmx_native.h"
 #include "bpmx_synth.h"
 
@@ -58,6 +60,20 @@ __global__ __launch_bounds__(256) void k_synth_pcm(uint64_t seed0, int n_files, 
 int beats_cap(int64_t n_frames, int32_t fs) {
     int64_t q = fs / 4 > 0 ? fs / 4 : 1;
     return (int)(n_frames / q) + 16;
+}
+
+/* the beat stages over the peak table: one launch sized by the plan; the
+ * global workspace (recordings beyond the LDS budget) is context scratch */
+int beats_stage(bpmx_ctx *ctx, const BeatsPlan &B, BeatsArgs &a, hipStream_t s) {
+    int rc = BPMX_OK;
+    a.lds_n = B.lds_n;
+    a.gws = nullptr;
+    if (B.any_global) {
+        a.gws = (unsigned char *)ctx->buf("beats_ws", B.gws, &rc);
+        if (rc != BPMX_OK) return rc;
+    }
+    LAUNCH(ctx, s, "k_beats", k_beats, dim3(B.grid), dim3(BEATS_T), B.lds, s, a);
+    return BPMX_OK;
 }
 
 }  // namespace
@@ -458,6 +474,33 @@ int bpmx_pack(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int3
         LAUNCH(ctx, s, "k_y16_quant", k_y16_quant, dim3(F, gm), dim3(PK_Y16_T), 0, s, a);
     }
     return BPMX_OK;
+}
+
+int bpmx_set_options(bpmx_ctx *ctx, int32_t options) {
+    if (!ctx) return fail(BPMX_E_ARG, "bpmx_set_options: ctx is NULL");
+    ctx->options = options;
+    return BPMX_OK;
+}
+
+int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
+                      double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
+                      const bpmx_beats_out *out, void *stream) {
+    if (!ctx || !params || !in || !out) return fail(BPMX_E_ARG, "bpmx_beats_device: NULL argument");
+    if (n_files < 1 || sr < 1) return fail(BPMX_E_ARG, "bpmx_beats_device: bad n_files/sr");
+    if (!in->pk_off || !in->pk_idx || !in->pk_env || !in->pk_floor || in->cap_peaks < 0 ||
+        in->cap_peaks >= (int64_t)INT_MAX)
+        return fail(BPMX_E_ARG, "bpmx_beats_device: needs the peak table (pk_off, pk_idx, pk_env, pk_floor) and "
+                                "0 <= cap_peaks < 2^31");
+    if (!out->final_idx || !out->n_final || !out->bpm_t || !out->bpm || !out->n_bpm || !out->status)
+        return fail(BPMX_E_ARG, "bpmx_beats_device: final_idx, n_final, bpm_t, bpm, n_bpm and status are required");
+    HIP_TRY(hipSetDevice(ctx->device));
+    BeatsArgs a{};
+    a.n_files = n_files; a.sr = sr; a.cap = in->cap_peaks;
+    a.pk_off = in->pk_off; a.pk_idx = in->pk_idx; a.pk_env = in->pk_env; a.pk_floor = in->pk_floor;
+    a.flags = flags; a.hint = start_bpm_hint; a.P = *params;
+    a.final_idx = out->final_idx; a.n_final = out->n_final; a.bpm_t = out->bpm_t; a.bpm = out->bpm;
+    a.n_bpm = out->n_bpm; a.pass = out->pass; a.tags = out->tags; a.status = out->status;
+    return beats_stage(ctx, beats_plan(n_files, in->cap_peaks, ctx->options), a, (hipStream_t)stream);
 }
 
 }  // extern "C"

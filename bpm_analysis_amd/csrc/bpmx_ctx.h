@@ -53,6 +53,7 @@ struct bpmx_ctx {
     std::vector<double> nat_ttab;               /* tail tables of k_native_carry (host copy) */
     std::vector<double> nat_tkey2;              /* their key: the sos coefficients and zi */
     bool nat_ttab_dirty = false;
+    int32_t options = 0;          /* bpmx_set_options: bits for the entry points that take no bpmx_params */
     bool prof = false;
     hipEvent_t stats_ev = nullptr;               /* recorded after the last run with BPMX_OPT_STATS */
     struct Rec { std::string name; hipEvent_t a, b; };

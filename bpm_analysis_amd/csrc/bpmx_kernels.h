@@ -510,6 +510,25 @@ __global__ void k_pack_gather(PackArgs A);
 __global__ void k_y16_max(Y16Args A);
 __global__ void k_y16_quant(Y16Args A);
 
+/* bpmx_beats_device (k_beats.hip): one wave64 workgroup per recording */
+enum { BEATS_T = 64 };
+struct BeatsArgs {
+    int32_t n_files, sr;
+    int64_t cap;                /* table capacity, entries */
+    int64_t lds_n;              /* recordings of at most this many peaks keep their workspace in LDS (-1: none) */
+    const int64_t *pk_off;      /* [F+1] */
+    const int32_t *pk_idx;
+    const double *pk_env, *pk_floor;
+    const int32_t *flags;       /* optional [F] bpmx_file_flag bits */
+    unsigned char *gws;         /* workspaces of the other recordings (bpmx_plan.h beats_plan) */
+    double hint;
+    int32_t *final_idx, *n_final, *n_bpm, *status;
+    double *bpm_t, *bpm, *pass; /* pass optional */
+    int8_t *tags;               /* optional */
+    bpmx_beat_params P;
+};
+__global__ void k_beats(BeatsArgs A);
+
 }  // namespace bpmx
 
 #endif

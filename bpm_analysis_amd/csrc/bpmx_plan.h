@@ -11,6 +11,7 @@
 #include <climits>
 #include <cstdio>
 
+#include "bpmx_beats_core.h"
 #include "bpmx_kernels.h"
 
 namespace bpmx {
@@ -183,6 +184,35 @@ inline RefEnvPlan ref_env_plan(int64_t maxnd, int32_t env_window, int32_t option
         R.kend[R.nkc++] = maxnd;
     }
     return R;
+}
+
+/* bpmx_beats_device: one wave64 workgroup per recording (k_beats).  A
+ * recording's workspace (bpmx_beats_core.h) with its copy of idx and env_pk
+ * lives in LDS when it fits BEATS_LDS_BUDGET: a quarter of a CU's 160 KB, so
+ * four workgroups (one wave per SIMD) share a CU, and the 605 peaks a 60 s
+ * recording can have (peak_capacity(18124, 30)) are inside it.  Longer tables
+ * take a slice of one global buffer at f * BEATS_WS_FIXED + BEATS_WS_STRIDE *
+ * pk_off[f].  Sized from the table capacity and the file count alone: the
+ * kernel reads pk_off itself, the launch needs no host synchronisation. */
+constexpr size_t BEATS_LDS_BUDGET = 40 * 1024;
+
+struct BeatsPlan {
+    unsigned grid;              /* workgroups: one per recording */
+    int64_t lds_n;              /* most peaks of an LDS-path recording (-1: every recording goes global) */
+    size_t lds;                 /* dynamic LDS bytes per workgroup */
+    bool any_global;            /* the capacity allows a recording beyond lds_n */
+    size_t gws;                 /* bytes of the global workspace buffer (0: none) */
+};
+
+inline BeatsPlan beats_plan(int F, int64_t cap_peaks, int32_t options, size_t budget = BEATS_LDS_BUDGET) {
+    BeatsPlan B{};
+    B.grid = (unsigned)F;
+    const bool forced = (options & BPMX_OPT_BEATS_GLOBAL) != 0;
+    B.lds_n = forced ? -1 : std::min<int64_t>(cap_peaks, beats_ws_max_peaks(budget));
+    B.lds = forced ? 0 : beats_ws_bytes(B.lds_n, true);
+    B.any_global = forced || cap_peaks > B.lds_n;
+    B.gws = B.any_global ? (size_t)F * BEATS_WS_FIXED + (size_t)cap_peaks * BEATS_WS_STRIDE : 0;
+    return B;
 }
 
 }  // namespace bpmx

@@ -183,7 +183,83 @@ class Packed:
         return out
 
 
-_NP_OF = {"torch.int16": np.int16, "torch.int32": np.int32, "torch.int64": np.int64, "torch.float64": np.float64}
+_NP_OF = {"torch.int8": np.int8, "torch.int16": np.int16, "torch.int32": np.int32, "torch.int64": np.int64,
+          "torch.float64": np.float64}
+
+
+@dataclass
+class Beats:
+    """bpmx_beats_device's outputs for one batch (device tensors): per
+    recording the final beats, the smoothed BPM curve, the preliminary pass'
+    values, one label per raw peak and a status, in slices that start at
+    ``packed.pk_off[f]`` like the peak table's."""
+    det: "object"
+    packed: Packed
+    final_idx: "object"
+    n_final: "object"
+    bpm_t: "object"
+    bpm: "object"
+    n_bpm: "object"
+    pass_: "object"
+    tags: "object"
+    status: "object"
+
+    def to_host(self) -> List[dict]:
+        """Per-file dicts as ``_host.beats`` returns them (final_peaks,
+        bpm_times, bpm, start_bpm, peak_time, recovery_time, tags, or
+        ``error=KeyError(...)`` for < 2 raw peaks) plus ``raw_peaks`` and
+        ``flags``; a recording the stage skipped (too short, bad window) gives
+        ``skipped=True`` with its flags.  Two rounds of copies like
+        ``Packed.to_host``: offsets, counts, status and pass values first, then
+        the used prefix of each array.  Raises BpmxError (E_LIMIT) when the
+        peak table was too small."""
+        from . import _host
+        torch = _torch()
+        det, pk = self.det, self.packed
+        F = pk.n_files
+        with det.lock:
+            st = torch.cuda.current_stream(det.device)
+            small = {"pk_off": pk.pk_off, "flags": pk.flags, "b_n_final": self.n_final, "b_n_bpm": self.n_bpm,
+                     "b_status": self.status, "b_pass": self.pass_}
+            pin = {k: det.staging(k, t.numel(), t.dtype) for k, t in small.items() if t is not None}
+            for k, h in pin.items():
+                h.copy_(small[k].reshape(-1), non_blocking=True)
+            st.synchronize()
+            meta = {k: h.numpy().copy() for k, h in pin.items()}
+            pko = meta["pk_off"]
+            tp = int(pko[F])
+            if tp > pk.cap_peaks or (meta["b_status"] == N.BEATS_OVERFLOW).any():
+                raise N.BpmxError(f"packed tables too small: {tp} peaks (capacity {pk.cap_peaks})", N.E_LIMIT)
+            big = {"pk_idx": pk.pk_idx, "b_final": self.final_idx, "b_bpm_t": self.bpm_t, "b_bpm": self.bpm,
+                   "b_tags": self.tags}
+            pin = {k: det.staging(k, tp, t.dtype) for k, t in big.items() if tp > 0}
+            for k, h in pin.items():
+                h.copy_(big[k][:tp], non_blocking=True)
+            st.synchronize()
+            tab = {k: (pin[k].numpy().copy() if k in pin else np.zeros(0, _NP_OF[str(t.dtype)]))
+                   for k, t in big.items()}
+        flags = meta["flags"] if "flags" in meta else np.zeros(F, np.int32)
+        pas = meta["b_pass"].reshape(F, 3)
+        raw, fin = tab["pk_idx"].astype(np.int64), tab["b_final"].astype(np.int64)
+        nan2none = lambda x: None if x != x else float(x)  # noqa: E731
+        out = []
+        for f in range(F):
+            a, s = int(pko[f]), int(meta["b_status"][f])
+            n, nf, nb = int(pko[f + 1]) - a, int(meta["b_n_final"][f]), int(meta["b_n_bpm"][f])
+            if s == N.BEATS_SKIPPED:
+                out.append({"skipped": True, "raw_peaks": np.zeros(0, np.int64), "flags": int(flags[f])})
+                continue
+            r = {"raw_peaks": raw[a:a + n], "flags": int(flags[f])}
+            if s == _host.E_FEW_PEAKS:
+                r["error"] = KeyError("dynamic_noise_floor_series")
+            elif s != _host.OK:
+                raise N.BpmxError(f"bpmx_beats_device: status {s} for recording {f}")
+            else:
+                r.update(final_peaks=fin[a:a + nf], bpm_times=tab["b_bpm_t"][a:a + nb], bpm=tab["b_bpm"][a:a + nb],
+                         start_bpm=float(pas[f, 0]), peak_time=nan2none(pas[f, 1]),
+                         recovery_time=nan2none(pas[f, 2]), tags=tab["b_tags"][a:a + n])
+            out.append(r)
+        return out
 
 
 class Detector:
@@ -618,6 +694,60 @@ class Detector:
             with self.lock, torch.cuda.stream(self.host_stream()):
                 res, d = self._batch_on_device(recs, fs, params, mode, stages, want_y16, resolve_ties)
                 out = self.pack(res, d.distance, want_y16=want_y16).to_host()
+                self.host_stream().synchronize()
+            return out
+
+        return self._in_callers_order(go, list(recordings), longest_first)
+
+    def beats_device(self, packed: Packed, params, hint: Optional[float] = None) -> Beats:
+        """bpmx_beats_device on the current stream, behind the ``pack`` that
+        filled `packed`: the beat stages (preliminary pass, classifier,
+        refinement, BPM curve) of every recording from its peak table, on the
+        GPU.  ``params``: the parameter dict or a prepared _host.BeatParams.
+        Asynchronous; outputs are sized by ``packed.cap_peaks``."""
+        from . import _host
+        torch = _torch()
+        bp = params if isinstance(params, _host.BeatParams) else _host.beat_params(params)
+        F, cap, dev = packed.n_files, max(int(packed.cap_peaks), 1), self.device
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        out = Beats(det=self, packed=packed, final_idx=e(cap, torch.int32), n_final=e(F, torch.int32),
+                    bpm_t=e(cap, torch.float64), bpm=e(cap, torch.float64), n_bpm=e(F, torch.int32),
+                    pass_=e(3 * F, torch.float64), tags=e(cap, torch.int8), status=e(F, torch.int32))
+        k = N.PackedOut()
+        k.cap_peaks = packed.cap_peaks
+        k.pk_off, k.pk_idx = packed.pk_off.data_ptr(), packed.pk_idx.data_ptr()
+        k.pk_env, k.pk_floor = packed.pk_env.data_ptr(), packed.pk_floor.data_ptr()
+        o = N.BeatsOut()
+        o.final_idx, o.n_final = out.final_idx.data_ptr(), out.n_final.data_ptr()
+        o.bpm_t, o.bpm, o.n_bpm = out.bpm_t.data_ptr(), out.bpm.data_ptr(), out.n_bpm.data_ptr()
+        o.pass_, o.tags, o.status = out.pass_.data_ptr(), out.tags.data_ptr(), out.status.data_ptr()
+        flags = None if packed.flags is None else packed.flags.data_ptr()
+        with self.lock:
+            N.check(self.L.bpmx_beats_device(self.ctx, F, int(packed.sr), ctypes.byref(bp),
+                                             float("nan") if hint is None else float(hint), ctypes.byref(k), flags,
+                                             ctypes.byref(o), self.stream_handle()), "bpmx_beats_device")
+        return out
+
+    def set_options(self, options: int) -> None:
+        """Context-level option bits (N.OPT_BEATS_GLOBAL; test/diagnostic)."""
+        with self.lock:
+            N.check(self.L.bpmx_set_options(self.ctx, int(options)), "bpmx_set_options")
+
+    def run_host_beats(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
+                       hint: Optional[float] = None, resolve_ties: bool = True,
+                       longest_first: bool = True) -> List[dict]:
+        """PCM on the host in, beats and BPM curves out, with no host stage in
+        between: upload, run, ``resolve_ties``, ``pack``, ``beats_device`` and
+        ``Beats.to_host``'s per-file dicts.  Same lock, stream and
+        longest-first rules as ``run_host_packed``."""
+        torch = _torch()
+        if not recordings:
+            return []
+
+        def go(recs):
+            with self.lock, torch.cuda.stream(self.host_stream()):
+                res, d = self._batch_on_device(recs, fs, params, mode, N.STAGE_ALL, False, resolve_ties)
+                out = self.beats_device(self.pack(res, d.distance), params, hint).to_host()
                 self.host_stream().synchronize()
             return out
 

@@ -71,11 +71,12 @@ def _load(it, fs):
     return fs, np.asarray(it)
 
 
-def _detect_local(items, idx, fs, params, mode, detector, packed=False):
+def _detect_local(items, idx, fs, params, mode, detector, packed=False, device_beats=False, hint=None):
     """The hot path over this rank's recordings: one ragged batch per (rate,
     sample format, channels), as dropin.analyze_wav_files groups them.
     `packed`: the detector's packed download (``run_host_packed``: per-peak
-    tables instead of whole envelopes)."""
+    tables instead of whole envelopes).  `device_beats`: the beat stages on
+    the GPU as well (``run_host_beats``: final beats and curves come back)."""
     from . import _native as N
     from .design import design
     from .dropin import DISTANCE_MSG, PADLEN_MSG, _file_error
@@ -96,8 +97,12 @@ def _detect_local(items, idx, fs, params, mode, detector, packed=False):
             d = design(f, params, log=False)
             if d.distance < 1:
                 raise ValueError(DISTANCE_MSG)
-            run = detector.run_host_packed if packed else detector.run_host
-            out = run([data[i][1] for i in ids], f, params, mode=mode, stages=N.STAGE_ALL, resolve_ties=True)
+            if device_beats:
+                out = detector.run_host_beats([data[i][1] for i in ids], f, params, mode=mode, hint=hint,
+                                              resolve_ties=True)
+            else:
+                run = detector.run_host_packed if packed else detector.run_host
+                out = run([data[i][1] for i in ids], f, params, mode=mode, stages=N.STAGE_ALL, resolve_ties=True)
         except (ValueError, N.BpmxError) as exc:
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                   # HIP / device failure: the rank fails, not the files
@@ -138,7 +143,11 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
       ``chunk_frames`` frames), and the host beat stages of each chunk on
       ``host_threads`` host threads while the GPU runs the next chunk
       (``beats="native"``: libbpmx_host.so, beats.analyze_fast;
-      ``"python"``: beats.analyze_recording; False: raw peaks only).
+      ``"python"``: beats.analyze_recording; False: raw peaks only;
+      ``"device"``: the beat stages on the GPU too, from the packed tables
+      where they lie (``run_host_beats``, bpmx_beats_device), so only beats
+      and curves come back and the host threads have nothing left to do; a
+      detector without ``run_host_beats`` behaves exactly as ``"native"``).
       The records below need the raw peaks, the beats and the curve only, and
       the native beat stage reads env and floor at the raw peaks alone, so
       with ``beats`` "native" or False and a detector that offers
@@ -185,6 +194,9 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
             if "error" in r:
                 out.append(FileResult(i, error=r["error"]))
                 continue
+            if device_beats:                           # the GPU ran the beat stages (run_host_beats)
+                out.append(FileResult(i, r["raw_peaks"], r["final_peaks"], r["bpm_times"], r["bpm"], int(r["flags"])))
+                continue
             pk = np.asarray(r["peaks"], dtype=np.int64)
             if not beats:
                 out.append(FileResult(i, raw_peaks=pk, flags=int(r["flags"])))
@@ -209,6 +221,9 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
                 out.append(FileResult(i, pk, a["final_peaks"], a["bpm_times"], a["bpm"], int(r["flags"])))
         return out
 
+    device_beats = beats == "device" and hasattr(detector, "run_host_beats")
+    if beats == "device" and not device_beats:
+        beats = "native"                               # a detector without the device stage: the host library
     use_packed = bool(packed) and beats != "python" and hasattr(detector, "run_host_packed")
     bparams = None
     if beats and beats != "python":
@@ -219,7 +234,7 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
     with ThreadPoolExecutor(host_threads) as ex:
         futs = []
         for idx in chunks:                             # the GPU runs chunk k+1 while host threads take chunk k
-            det_res = _detect_local(items, idx, fs, params, mode, detector, use_packed)
+            det_res = _detect_local(items, idx, fs, params, mode, detector, use_packed, device_beats, start_bpm_hint)
             per = max(1, len(idx) // host_threads)
             futs += [ex.submit(host_stage, idx[a:a + per], det_res) for a in range(0, len(idx), per)]
         for fu in futs:

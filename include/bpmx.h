@@ -13,6 +13,10 @@
  *   bpmx_run(stages=PEAKS)     <- bpm_analysis.py:223-229    PeakClassifier._find_raw_peaks
  *   bpmx_run(stages=ALL)       <- the three above in sequence, as analyze_wav_file
  *                                 runs them (bpm_analysis.py:1731-1732, :89)
+ *   bpmx_pack                  the results as per-peak / per-trough tables
+ *   bpmx_beats_device          <- bpm_analysis.py:1734-1757  analyze_wav_file stages 2-5 on
+ *                                 those tables (_run_preliminary_pass, PeakClassifier,
+ *                                 _refine_and_correct_peaks, calculate_bpm_series)
  *   bpmx_synth / bpmx_synth_host   deterministic synthetic recordings (bench/tests)
  *
  * Plain C types only.  PCM and result arrays are DEVICE pointers (HBM); the
@@ -29,11 +33,13 @@
 
 #include <stdint.h>
 
+#include "bpmx_host.h" /* bpmx_beat_params, bpmx_beat_tag, bpmx_host_status (bpmx_beats_device) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define BPMX_ABI_VERSION 3
+#define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
 enum bpmx_dtype { BPMX_DT_U8 = 0, BPMX_DT_I16 = 1, BPMX_DT_I32 = 2, BPMX_DT_F32 = 3, BPMX_DT_F64 = 4 };
@@ -116,9 +122,12 @@ enum bpmx_option {
     BPMX_OPT_STATS = 2048,           /* count the run's path decisions for bpmx_stats (diagnostic) */
     BPMX_OPT_HILBERT_BLUESTEIN = 4096, /* native mode, long recordings: rocFFT Bluestein instead of the exact-
                                          length four-step transform (test/diagnostic) */
-    BPMX_OPT_REF_NOSPLIT = 8192      /* reference mode: gather every decimated sample first, then the forward
+    BPMX_OPT_REF_NOSPLIT = 8192,     /* reference mode: gather every decimated sample first, then the forward
                                         pass inside k_envelope_ref, instead of forward-pass row chunks
                                         overlapping the next chunks' gather on a side stream (diagnostic) */
+    BPMX_OPT_BEATS_GLOBAL = 16384    /* bpmx_beats_device (set with bpmx_set_options): every recording's
+                                        workspace in global memory instead of LDS for the tables that fit
+                                        there (test/diagnostic) */
 };
 
 /* bpmx_stats counters of the last run with BPMX_OPT_STATS */
@@ -272,6 +281,52 @@ typedef struct {
  * it).  No host synchronisation; scratch comes from ctx. */
 int bpmx_pack(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, const bpmx_out *in,
               const bpmx_packed *out, void *stream);
+
+/* The beat stages on the device (bpmx_beats_device).
+ *
+ * What the reference runs per file after the hot path (bpm_analysis.py
+ * :1734-1757: _run_preliminary_pass, PeakClassifier.classify_peaks,
+ * _refine_and_correct_peaks, calculate_bpm_series), computed from bpmx_pack's
+ * peak table where it lies.  The arithmetic is that of bpmx_beats
+ * (bpmx_host.h), one statement of it for both (csrc/bpmx_beats_core.h):
+ * every index, label, count and pass value equals the host library's, and
+ * the curves are the same IEEE f64 operations in the same order.
+ *
+ * Per-file output slices start at pk_off[f], like the peak table's; a file
+ * writes n_final[f] / n_bpm[f] entries of its slices and nothing else (tags:
+ * one per raw peak).  pass and tags are optional (NULL). */
+enum bpmx_beats_status {        /* bpmx_beats_out.status, beside BPMX_HOST_OK and BPMX_HOST_E_FEW_PEAKS
+                                   (< 2 raw peaks: counts 0, tags still written, as on the host) */
+    BPMX_BEATS_SKIPPED = -16,   /* flags given and the file carries BPMX_F_TOO_SHORT or BPMX_F_BAD_WINDOW:
+                                   counts 0, pass NaN, no tags */
+    BPMX_BEATS_OVERFLOW = -17   /* the file's table slice reaches past cap_peaks (or its offsets are not
+                                   ascending): counts 0, pass NaN, nothing read or written beyond the capacity */
+};
+
+typedef struct {            /* device; per-file slices start at pk_off[f], like the peak table */
+    int32_t *final_idx;     /* [cap_peaks] final beats (subset of the raw peaks, ascending) */
+    int32_t *n_final;       /* [n_files] */
+    double  *bpm_t, *bpm;   /* [cap_peaks] curve rows, n_bpm[f] valid */
+    int32_t *n_bpm;         /* [n_files] */
+    double  *pass;          /* optional [n_files][3]: start BPM, peak-BPM time, recovery end (NaN = None) */
+    int8_t  *tags;          /* optional [cap_peaks] bpmx_beat_tag per raw peak */
+    int32_t *status;        /* [n_files] */
+} bpmx_beats_out;
+
+/* The beat stages of n_files recordings at decimated rate sr from the peak
+ * table `in` (pk_off, pk_idx, pk_env, pk_floor and cap_peaks < 2^31 required;
+ * pk_idx strictly increasing per file, as bpmx_pack writes it), asynchronously
+ * on `stream`, ordered after the pack.  start_bpm_hint: NaN = None.  flags:
+ * optional device [n_files] (bpmx_out.flags).  Never synchronises the host;
+ * scratch comes from ctx (grown on the first call of a capacity).  One wave64
+ * workgroup per recording; see csrc/k_beats.hip. */
+int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
+                      double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
+                      const bpmx_beats_out *out, void *stream);
+
+/* bpmx_option bits for the entry points that take no bpmx_params
+ * (BPMX_OPT_BEATS_GLOBAL); they hold until set again. */
+int bpmx_set_options(bpmx_ctx *ctx, int32_t options);
 
 /* Synthetic int16 recordings straight into HBM: file f gets seed seed0+f,
  * frames [frame_offsets[f], frame_offsets[f+1]) of pcm (device). */
