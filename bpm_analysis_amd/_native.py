@@ -37,13 +37,19 @@ OPT_STATS = 2048
 OPT_HILBERT_BLUESTEIN = 4096
 OPT_REF_NOSPLIT = 8192
 OPT_BEATS_GLOBAL = 16384           # bpmx_beats_device, through bpmx_set_options (test/diagnostic)
+OPT_METRICS_GLOBAL = 32768         # bpmx_metrics_device, through bpmx_set_options (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS
+# bpmx_metrics_out.status: 0, the two bits, or a negative code
+METRICS_OK, METRICS_TIE, METRICS_E_DISTANCE, METRICS_NONE, METRICS_OVERFLOW = 0, 1, 2, -18, -19
+# bpmx_metrics_out.record (16 doubles per file, NaN = absent)
+MR_AVG_BPM, MR_MIN_BPM, MR_MAX_BPM, MR_AVG_RMSSDC, MR_AVG_SDNN = 0, 1, 2, 3, 4
+MR_HRR_PEAK, MR_HRR_RECOVERY_BPM, MR_HRR_VALUE, MR_RECOVERY, MR_EXERTION, METRICS_RECORD = 5, 6, 7, 8, 12, 16
 
 EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy", "bpmx_decimated_length",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
-           "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options"]
+           "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device"]
 
 
 class Params(ctypes.Structure):
@@ -92,6 +98,28 @@ class BeatsOut(ctypes.Structure):
     _fields_ = [("final_idx", ctypes.c_void_p), ("n_final", ctypes.c_void_p), ("bpm_t", ctypes.c_void_p),
                 ("bpm", ctypes.c_void_p), ("n_bpm", ctypes.c_void_p), ("pass_", ctypes.c_void_p),
                 ("tags", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class MetricParams(ctypes.Structure):
+    """bpmx_metric_params: the two HRV keys of DEFAULT_PARAMS and the defaults
+    the reference calls its slope, HRR and incline / decline functions with."""
+    _fields_ = [("hrv_window_size_beats", ctypes.c_int32), ("hrv_step_size_beats", ctypes.c_int32),
+                ("min_duration_sec", ctypes.c_double), ("min_bpm_change", ctypes.c_double),
+                ("prominence", ctypes.c_double), ("slope_window_sec", ctypes.c_double),
+                ("hrr_interval_sec", ctypes.c_double)]
+
+
+def metric_params(params: dict) -> MetricParams:
+    return MetricParams(int(params["hrv_window_size_beats"]), int(params["hrv_step_size_beats"]),
+                        10.0, 15.0, 5.0, 20.0, 60.0)
+
+
+class MetricsOut(ctypes.Structure):
+    """bpmx_metrics_out: the device arrays bpmx_metrics_device fills (per-file
+    slices at pk_off[f]; every pointer required)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "hrv_time", "hrv_rmssdc", "hrv_sdnn", "hrv_bpm", "n_hrv", "inc_a", "inc_b", "dec_a", "dec_b",
+        "inc_slope", "inc_dur", "dec_slope", "dec_dur", "n_inc", "n_dec", "record", "status")]
 
 
 class BpmxError(RuntimeError):
@@ -165,6 +193,10 @@ def load() -> ctypes.CDLL:
         L.bpmx_beats_device.restype = ctypes.c_int
         L.bpmx_set_options.argtypes = [P, I32]
         L.bpmx_set_options.restype = ctypes.c_int
+    if hasattr(L, "bpmx_metrics_device"):
+        L.bpmx_metrics_device.argtypes = [P, I32, I32, ctypes.POINTER(MetricParams), I64, ctypes.POINTER(PackedOut),
+                                          ctypes.POINTER(BeatsOut), ctypes.POINTER(MetricsOut), P]
+        L.bpmx_metrics_device.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

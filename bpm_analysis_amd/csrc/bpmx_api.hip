@@ -76,6 +76,25 @@ int beats_stage(bpmx_ctx *ctx, const BeatsPlan &B, BeatsArgs &a, hipStream_t s) 
     return BPMX_OK;
 }
 
+/* the final metrics behind the beat stages: one launch sized by the plan */
+int metrics_stage(bpmx_ctx *ctx, const MetricsPlan &M, int32_t n_files, int32_t sr, const bpmx_metric_params &P,
+                  int64_t epoch_us, const bpmx_packed &t, const bpmx_beats_out &b, const bpmx_metrics_out &o,
+                  hipStream_t s) {
+    int rc = BPMX_OK;
+    MetricsArgs a{};
+    a.n_files = n_files; a.sr = sr; a.cap = t.cap_peaks; a.lds_n = M.lds_n; a.epoch_us = epoch_us;
+    a.fw = M.fw; a.fixed = M.fixed; a.pk_off = t.pk_off;
+    a.final_idx = b.final_idx; a.n_final = b.n_final; a.n_bpm = b.n_bpm; a.b_status = b.status;
+    a.bpm_t = b.bpm_t; a.bpm = b.bpm;
+    a.P = P; a.O = o;
+    if (M.any_global) {
+        a.gws = (unsigned char *)ctx->buf("metrics_ws", M.gws, &rc);
+        if (rc != BPMX_OK) return rc;
+    }
+    LAUNCH(ctx, s, "k_metrics", k_metrics, dim3(M.grid), dim3(METRICS_T), M.lds, s, a);
+    return BPMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -501,6 +520,27 @@ int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_bea
     a.final_idx = out->final_idx; a.n_final = out->n_final; a.bpm_t = out->bpm_t; a.bpm = out->bpm;
     a.n_bpm = out->n_bpm; a.pass = out->pass; a.tags = out->tags; a.status = out->status;
     return beats_stage(ctx, beats_plan(n_files, in->cap_peaks, ctx->options), a, (hipStream_t)stream);
+}
+
+int bpmx_metrics_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_metric_params *params,
+                        int64_t epoch_us, const bpmx_packed *tables, const bpmx_beats_out *beats,
+                        const bpmx_metrics_out *out, void *stream) {
+    if (!ctx || !params || !tables || !beats || !out) return fail(BPMX_E_ARG, "bpmx_metrics_device: NULL argument");
+    if (n_files < 1 || sr < 1) return fail(BPMX_E_ARG, "bpmx_metrics_device: bad n_files/sr");
+    if (params->hrv_window_size_beats < 2 || params->hrv_step_size_beats < 1)
+        return fail(BPMX_E_ARG, "bpmx_metrics_device: needs hrv_window_size_beats >= 2 and hrv_step_size_beats >= 1");
+    if (!tables->pk_off || tables->cap_peaks < 0 || tables->cap_peaks >= (int64_t)INT_MAX)
+        return fail(BPMX_E_ARG, "bpmx_metrics_device: needs pk_off and 0 <= cap_peaks < 2^31");
+    if (!beats->final_idx || !beats->n_final || !beats->bpm_t || !beats->bpm || !beats->n_bpm || !beats->status)
+        return fail(BPMX_E_ARG, "bpmx_metrics_device: the beats' final_idx, n_final, bpm_t, bpm, n_bpm and status "
+                                "are required");
+    if (!out->hrv_time || !out->hrv_rmssdc || !out->hrv_sdnn || !out->hrv_bpm || !out->n_hrv || !out->inc_a ||
+        !out->inc_b || !out->dec_a || !out->dec_b || !out->inc_slope || !out->inc_dur || !out->dec_slope ||
+        !out->dec_dur || !out->n_inc || !out->n_dec || !out->record || !out->status)
+        return fail(BPMX_E_ARG, "bpmx_metrics_device: every pointer of bpmx_metrics_out is required");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return metrics_stage(ctx, metrics_plan(n_files, tables->cap_peaks, ctx->options, params->hrv_window_size_beats),
+                         n_files, sr, *params, epoch_us, *tables, *beats, *out, (hipStream_t)stream);
 }
 
 }  // extern "C"

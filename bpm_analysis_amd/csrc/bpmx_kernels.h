@@ -529,6 +529,24 @@ struct BeatsArgs {
 };
 __global__ void k_beats(BeatsArgs A);
 
+/* bpmx_metrics_device (k_metrics.hip): one workgroup of METRICS_T threads per recording */
+enum { METRICS_T = 256 };
+struct MetricsArgs {
+    int32_t n_files, sr;
+    int64_t cap;                /* table capacity, entries */
+    int64_t lds_n;              /* recordings of at most this many peaks work in LDS (-1: none) */
+    int64_t epoch_us;
+    int32_t fw;                 /* pairwise-sum frames per lane (pw_frames of the HRV window) */
+    size_t fixed;               /* metrics_ws_fixed(METRICS_T, fw): a global slice starts at f * fixed + MX_STRIDE * pk_off[f] */
+    const int64_t *pk_off;      /* [F+1] */
+    const int32_t *final_idx, *n_final, *n_bpm, *b_status;   /* k_beats' outputs */
+    const double *bpm_t, *bpm;
+    unsigned char *gws;         /* workspaces of the recordings beyond lds_n (bpmx_plan.h metrics_plan) */
+    bpmx_metric_params P;
+    bpmx_metrics_out O;
+};
+__global__ void k_metrics(MetricsArgs A);
+
 }  // namespace bpmx
 
 #endif

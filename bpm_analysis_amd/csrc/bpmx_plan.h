@@ -12,6 +12,7 @@
 #include <cstdio>
 
 #include "bpmx_beats_core.h"
+#include "bpmx_metrics_core.h"
 #include "bpmx_kernels.h"
 
 namespace bpmx {
@@ -213,6 +214,42 @@ inline BeatsPlan beats_plan(int F, int64_t cap_peaks, int32_t options, size_t bu
     B.any_global = forced || cap_peaks > B.lds_n;
     B.gws = B.any_global ? (size_t)F * BEATS_WS_FIXED + (size_t)cap_peaks * BEATS_WS_STRIDE : 0;
     return B;
+}
+
+/* bpmx_metrics_device: one workgroup of METRICS_T threads per recording
+ * (k_metrics).  A recording's workspace (bpmx_metrics_core.h) with its copy of
+ * the curve and the beats lives in LDS when it fits METRICS_LDS_BUDGET: 48 KB,
+ * so three workgroups share a CU's 160 KB, and the 605 peaks a 60 s recording
+ * can have are inside it at the default HRV window.  A window beyond 128 beats
+ * gives every thread a stack for its pairwise sums, which takes from the
+ * budget.  Longer tables take a slice of one global buffer at f * fixed +
+ * MX_STRIDE * pk_off[f].  Sized like beats_plan from the capacity and the file
+ * count alone. */
+constexpr size_t METRICS_LDS_BUDGET = 48 * 1024;
+
+struct MetricsPlan {
+    unsigned grid;              /* workgroups: one per recording */
+    int fw;                     /* pairwise-sum frames per thread */
+    int64_t lds_n;              /* most peaks of an LDS-path recording (-1: every recording goes global) */
+    size_t lds;                 /* dynamic LDS bytes per workgroup */
+    bool any_global;
+    size_t fixed;               /* metrics_ws_fixed(METRICS_T, fw) */
+    size_t gws;                 /* bytes of the global workspace buffer (0: none) */
+};
+
+inline MetricsPlan metrics_plan(int F, int64_t cap_peaks, int32_t options, int32_t hrv_window,
+                                size_t budget = METRICS_LDS_BUDGET) {
+    MetricsPlan M{};
+    M.grid = (unsigned)F;
+    M.fw = pw_frames(hrv_window);
+    const bool forced = (options & BPMX_OPT_METRICS_GLOBAL) != 0;
+    M.lds_n = forced ? -1 : std::min<int64_t>(cap_peaks, metrics_ws_max_n(budget, METRICS_T, M.fw));
+    if (!forced && metrics_ws_head(METRICS_T, M.fw) > budget) M.lds_n = -1;   /* the stacks alone exceed the budget */
+    M.lds = M.lds_n < 0 ? 0 : metrics_ws_bytes(M.lds_n, METRICS_T, M.fw, true);
+    M.any_global = cap_peaks > M.lds_n;
+    M.fixed = metrics_ws_fixed(METRICS_T, M.fw);
+    M.gws = M.any_global ? (size_t)F * M.fixed + (size_t)cap_peaks * MX_STRIDE : 0;
+    return M;
 }
 
 }  // namespace bpmx

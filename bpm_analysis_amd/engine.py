@@ -262,6 +262,113 @@ class Beats:
         return out
 
 
+_METRIC_ROWS = ("hrv_time", "hrv_rmssdc", "hrv_sdnn", "hrv_bpm", "inc_a", "inc_b", "dec_a", "dec_b",
+                "inc_slope", "inc_dur", "dec_slope", "dec_dur")
+
+
+@dataclass
+class Metrics:
+    """bpmx_metrics_device's outputs for one batch (device tensors): per
+    recording the windowed HRV rows, the major inclines and declines as curve
+    positions in report order, the 16-double record (summary, HRR, steepest
+    recovery and exertion; NaN = absent) and a status, in slices that start
+    at ``packed.pk_off[f]``."""
+    det: "object"
+    beats: Beats
+    params: dict
+    epoch_us: int
+    hrv_time: "object"
+    hrv_rmssdc: "object"
+    hrv_sdnn: "object"
+    hrv_bpm: "object"
+    n_hrv: "object"
+    inc_a: "object"
+    inc_b: "object"
+    dec_a: "object"
+    dec_b: "object"
+    inc_slope: "object"
+    inc_dur: "object"
+    dec_slope: "object"
+    dec_dur: "object"
+    n_inc: "object"
+    n_dec: "object"
+    record: "object"
+    status: "object"
+
+    def download(self, rows: bool = True):
+        """(meta, tab): the per-file counts, status and records, then (with
+        `rows`) the used prefix of each per-peak array, in two rounds of pinned
+        copies."""
+        torch = _torch()
+        det, pk = self.det, self.beats.packed
+        F = pk.n_files
+        with det.lock:
+            st = torch.cuda.current_stream(det.device)
+            small = {"pk_off": pk.pk_off, "m_n_hrv": self.n_hrv, "m_n_inc": self.n_inc, "m_n_dec": self.n_dec,
+                     "m_status": self.status, "m_record": self.record}
+            pin = {k: det.staging(k, t.numel(), t.dtype) for k, t in small.items()}
+            for k, h in pin.items():
+                h.copy_(small[k].reshape(-1), non_blocking=True)
+            st.synchronize()
+            meta = {k: h.numpy().copy() for k, h in pin.items()}
+            tp = int(meta["pk_off"][F])
+            if tp > pk.cap_peaks or (meta["m_status"] == N.METRICS_OVERFLOW).any():
+                raise N.BpmxError(f"packed tables too small: {tp} peaks (capacity {pk.cap_peaks})", N.E_LIMIT)
+            big = {"m_" + k: getattr(self, k) for k in _METRIC_ROWS} if rows else {}
+            pin = {k: det.staging(k, tp, t.dtype) for k, t in big.items() if tp > 0}
+            for k, h in pin.items():
+                h.copy_(big[k][:tp], non_blocking=True)
+            st.synchronize()
+            tab = {k[2:]: (pin[k].numpy().copy() if k in pin else np.zeros(0, _NP_OF[str(t.dtype)]))
+                   for k, t in big.items()}
+        meta["m_record"] = meta["m_record"].reshape(F, N.METRICS_RECORD)
+        return meta, tab
+
+    def to_host(self, assemble: bool = True) -> List[dict]:
+        """``Beats.to_host()``'s per-file dicts plus ``final_metrics`` (the dict
+        ``beats.final_metrics`` returns, assembled from the device's positions
+        and values; None where the reference makes none: fewer than two final
+        beats, an error, a skipped recording) and ``metrics_source``.  A
+        recording whose find_peaks met a decisive tie or an invalid distance
+        is recomputed by ``beats.final_metrics`` on the host (numpy's order,
+        scipy's ValueError as ``error``): ``metrics_source`` is then "host",
+        else "device".  ``beats._epoch()`` must be what it was at the launch.
+        ``assemble=False`` leaves the pandas objects out: instead of
+        ``final_metrics`` each dict gets ``metrics_record`` (the 16 doubles of
+        bpmx_metrics_out) and ``n_hrv``, which is all ``run_sharded`` gathers."""
+        from . import beats as B
+        from . import metrics as MH
+        out = self.beats.to_host()
+        meta, tab = self.download(rows=assemble)
+        pko, sr = meta["pk_off"], int(self.beats.packed.sr)
+        for f, r in enumerate(out):
+            s, a = int(meta["m_status"][f]), int(pko[f])
+            r["metrics_source"] = "device"
+            if s < 0 and s != N.METRICS_NONE:
+                raise N.BpmxError(f"bpmx_metrics_device: status {s} for recording {f}")
+            if s > 0:                                  # TIE or E_DISTANCE: numpy's order, scipy's exception
+                r["metrics_source"] = "host"
+                try:
+                    m = B.final_metrics(r["final_peaks"], sr, self.params)
+                except ValueError as e:
+                    m, r["error"] = None, e
+                if assemble:
+                    r["final_metrics"] = m
+                else:
+                    r["metrics_record"], r["n_hrv"] = MH.record_of(m)
+            elif not assemble:
+                r["metrics_record"], r["n_hrv"] = meta["m_record"][f].copy(), int(meta["m_n_hrv"][f])
+            elif s == N.METRICS_NONE:
+                r["final_metrics"] = None
+            else:
+                nh, ni, nd = int(meta["m_n_hrv"][f]), int(meta["m_n_inc"][f]), int(meta["m_n_dec"][f])
+                hrv = {c: tab["hrv_" + c][a:a + nh] for c in MH.HRV_COLS}
+                inc = {c: tab["inc_" + c][a:a + ni] for c in ("a", "b", "slope", "dur")}
+                dec = {c: tab["dec_" + c][a:a + nd] for c in ("a", "b", "slope", "dur")}
+                r["final_metrics"] = MH.assemble(r["bpm_times"], r["bpm"], meta["m_record"][f], hrv, inc, dec)
+        return out
+
+
 class Detector:
     """One libbpmx context on one GPU.
 
@@ -729,7 +836,7 @@ class Detector:
         return out
 
     def set_options(self, options: int) -> None:
-        """Context-level option bits (N.OPT_BEATS_GLOBAL; test/diagnostic)."""
+        """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL; test/diagnostic)."""
         with self.lock:
             N.check(self.L.bpmx_set_options(self.ctx, int(options)), "bpmx_set_options")
 
@@ -748,6 +855,60 @@ class Detector:
             with self.lock, torch.cuda.stream(self.host_stream()):
                 res, d = self._batch_on_device(recs, fs, params, mode, N.STAGE_ALL, False, resolve_ties)
                 out = self.beats_device(self.pack(res, d.distance), params, hint).to_host()
+                self.host_stream().synchronize()
+            return out
+
+        return self._in_callers_order(go, list(recordings), longest_first)
+
+    def metrics_device(self, beats: Beats, params: dict, epoch_us: Optional[int] = None) -> Metrics:
+        """bpmx_metrics_device on the current stream, behind the
+        ``beats_device`` that filled `beats`: the final metrics (windowed HRV
+        table, summary, HRR, steepest slopes, major inclines and declines) of
+        every recording from its beats and curve, on the GPU.  ``epoch_us``:
+        the origin of the curve's index (default ``beats._epoch()``).
+        Asynchronous; outputs are sized by the peak table's capacity."""
+        from . import metrics as MH
+        torch = _torch()
+        packed = beats.packed
+        mp = N.metric_params(params)
+        eu = MH.epoch_us() if epoch_us is None else int(epoch_us)
+        F, cap, dev = packed.n_files, max(int(packed.cap_peaks), 1), self.device
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        rows = {k: e(cap, torch.int32 if k[4:] in ("a", "b") else torch.float64) for k in _METRIC_ROWS}
+        out = Metrics(det=self, beats=beats, params=dict(params), epoch_us=eu, n_hrv=e(F, torch.int32),
+                      n_inc=e(F, torch.int32), n_dec=e(F, torch.int32),
+                      record=e(F * N.METRICS_RECORD, torch.float64), status=e(F, torch.int32), **rows)
+        k = N.PackedOut()
+        k.cap_peaks, k.pk_off = packed.cap_peaks, packed.pk_off.data_ptr()
+        b = N.BeatsOut()
+        b.final_idx, b.n_final = beats.final_idx.data_ptr(), beats.n_final.data_ptr()
+        b.bpm_t, b.bpm, b.n_bpm = beats.bpm_t.data_ptr(), beats.bpm.data_ptr(), beats.n_bpm.data_ptr()
+        b.status = beats.status.data_ptr()
+        o = N.MetricsOut()
+        for name, _ in N.MetricsOut._fields_:
+            setattr(o, name, getattr(out, name).data_ptr())
+        with self.lock:
+            N.check(self.L.bpmx_metrics_device(self.ctx, F, int(packed.sr), ctypes.byref(mp), eu, ctypes.byref(k),
+                                               ctypes.byref(b), ctypes.byref(o), self.stream_handle()),
+                    "bpmx_metrics_device")
+        return out
+
+    def run_host_metrics(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
+                         hint: Optional[float] = None, resolve_ties: bool = True,
+                         longest_first: bool = True, assemble: bool = True) -> List[dict]:
+        """``run_host_beats`` plus the final metrics on the device: PCM on the
+        host in, per file the dicts of ``Beats.to_host()`` with
+        ``final_metrics`` and ``metrics_source`` (``Metrics.to_host``) out;
+        ``assemble=False``: ``metrics_record`` and ``n_hrv`` in its place."""
+        torch = _torch()
+        if not recordings:
+            return []
+
+        def go(recs):
+            with self.lock, torch.cuda.stream(self.host_stream()):
+                res, d = self._batch_on_device(recs, fs, params, mode, N.STAGE_ALL, False, resolve_ties)
+                b = self.beats_device(self.pack(res, d.distance), params, hint)
+                out = self.metrics_device(b, params).to_host(assemble=assemble)
                 self.host_stream().synchronize()
             return out
 

@@ -71,12 +71,16 @@ def _load(it, fs):
     return fs, np.asarray(it)
 
 
-def _detect_local(items, idx, fs, params, mode, detector, packed=False, device_beats=False, hint=None):
+def _detect_local(items, idx, fs, params, mode, detector, packed=False, device_beats=False, hint=None,
+                  metrics=False, device_metrics=False):
     """The hot path over this rank's recordings: one ragged batch per (rate,
     sample format, channels), as dropin.analyze_wav_files groups them.
     `packed`: the detector's packed download (``run_host_packed``: per-peak
     tables instead of whole envelopes).  `device_beats`: the beat stages on
-    the GPU as well (``run_host_beats``: final beats and curves come back)."""
+    the GPU as well (``run_host_beats``: final beats and curves come back);
+    `metrics`: the results carry the decimated rate ``sr`` for the host's
+    ``final_metrics``; `device_metrics`: the final metrics on the GPU too
+    (``run_host_metrics``)."""
     from . import _native as N
     from .design import design
     from .dropin import DISTANCE_MSG, PADLEN_MSG, _file_error
@@ -98,8 +102,11 @@ def _detect_local(items, idx, fs, params, mode, detector, packed=False, device_b
             if d.distance < 1:
                 raise ValueError(DISTANCE_MSG)
             if device_beats:
-                out = detector.run_host_beats([data[i][1] for i in ids], f, params, mode=mode, hint=hint,
-                                              resolve_ties=True)
+                kw = dict(mode=mode, hint=hint, resolve_ties=True)
+                if device_metrics:                      # the records alone: no pandas objects per file
+                    out = detector.run_host_metrics([data[i][1] for i in ids], f, params, assemble=False, **kw)
+                else:
+                    out = detector.run_host_beats([data[i][1] for i in ids], f, params, **kw)
             else:
                 run = detector.run_host_packed if packed else detector.run_host
                 out = run([data[i][1] for i in ids], f, params, mode=mode, stages=N.STAGE_ALL, resolve_ties=True)
@@ -112,6 +119,8 @@ def _detect_local(items, idx, fs, params, mode, detector, packed=False, device_b
             continue
         for i, r in zip(ids, out):
             err = _file_error(r["flags"], params, d.sr)
+            if err is None and metrics:
+                r = dict(r, sr=d.sr)                    # the host's final_metrics needs the decimated rate
             res[i] = {"error": err} if err is not None else r
     return res
 
@@ -129,7 +138,7 @@ def _pad_rows(rows: List[np.ndarray], width: int, fill, dtype) -> np.ndarray:
 def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: str = "native",
                 start_bpm_hint: Optional[float] = None, beats="native", detector=None,
                 group=None, host_threads: int = 0, chunk_frames: int = 1 << 30,
-                packed: bool = True) -> Optional[List[dict]]:
+                packed: bool = True, metrics: bool = False) -> Optional[List[dict]]:
     """A ragged batch of independent recordings over the ranks of a
     torch.distributed process group (one process per GPU); the
     per-file loop it replaces is gui.py:202-251.
@@ -159,10 +168,19 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
       [files, 2 x BPM-curve points] per rank, padded to the widest over all
       ranks (caps agreed by one all_reduce(MAX)); errors as objects.
 
+    * ``metrics=True``: the final metrics per file as well, as the 16-double
+      record of bpmx_metrics_out (summary, HRR, steepest recovery and
+      exertion; positions into the curve, NaN = absent) and the HRV row
+      count, one more int64 column and 16 more f64 columns of the slabs.
+      With ``beats="device"`` and a detector that offers ``run_host_metrics``
+      they come from the GPU (bpmx_metrics_device); otherwise
+      ``beats.final_metrics`` runs on the host threads.
+
     Returns, on rank 0, one dict per item in order: ``raw_peaks``,
     ``final_peaks``, ``bpm_times``, ``bpm`` (the smoothed curve that
     ``<base>_bpm_plot.csv`` holds, bpm_analysis.py:1463-1484), ``flags``,
-    ``rank``, or ``error``; None on the other ranks."""
+    ``rank`` (with ``metrics``: ``metrics_record``, ``n_hrv``), or ``error``;
+    None on the other ranks."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -187,6 +205,26 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
     if cur:
         chunks.append(cur)
 
+    def add_metrics(row, r, known=None):
+        """The file's final metrics (the device's or analyze_recording's when
+        it has them, else computed here) as the record the gather carries."""
+        if not metrics or row.error is not None:
+            return row
+        from . import metrics as MH
+        if known is not None and "metrics_record" in known:    # the device's record as it came
+            row.record, row.n_hrv = known["metrics_record"], known["n_hrv"]
+            return row
+        if known is not None:
+            m = known["final_metrics"]
+        else:
+            from .beats import final_metrics
+            try:
+                m = final_metrics(row.final_peaks, r["sr"], params) if len(row.final_peaks) >= 2 else None
+            except ValueError as exc:                  # scipy rejects the find_peaks distance: this file only
+                return FileResult(row.index, error=exc)
+        row.record, row.n_hrv = MH.record_of(m)
+        return row
+
     def host_stage(idx, det_res):
         out = []
         for i in idx:
@@ -195,11 +233,12 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
                 out.append(FileResult(i, error=r["error"]))
                 continue
             if device_beats:                           # the GPU ran the beat stages (run_host_beats)
-                out.append(FileResult(i, r["raw_peaks"], r["final_peaks"], r["bpm_times"], r["bpm"], int(r["flags"])))
+                row = FileResult(i, r["raw_peaks"], r["final_peaks"], r["bpm_times"], r["bpm"], int(r["flags"]))
+                out.append(add_metrics(row, r, r if "metrics_source" in r else None))
                 continue
             pk = np.asarray(r["peaks"], dtype=np.int64)
             if not beats:
-                out.append(FileResult(i, raw_peaks=pk, flags=int(r["flags"])))
+                out.append(add_metrics(FileResult(i, raw_peaks=pk, flags=int(r["flags"])), r))
                 continue
             if beats == "python":
                 from .beats import analyze_recording
@@ -208,7 +247,7 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
                 except Exception as exc:               # per file, as the GUI loop catches it (gui.py:247-251)
                     out.append(FileResult(i, error=exc))
                     continue
-                out.append(FileResult.from_analysis(i, pk, int(r["flags"]), a))
+                out.append(add_metrics(FileResult.from_analysis(i, pk, int(r["flags"]), a), r, a))
                 continue
             from . import _host
             if "env_pk" in r:
@@ -218,12 +257,13 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
             if "error" in a:
                 out.append(FileResult(i, error=a["error"]))
             else:
-                out.append(FileResult(i, pk, a["final_peaks"], a["bpm_times"], a["bpm"], int(r["flags"])))
+                out.append(add_metrics(FileResult(i, pk, a["final_peaks"], a["bpm_times"], a["bpm"], int(r["flags"])), r))
         return out
 
     device_beats = beats == "device" and hasattr(detector, "run_host_beats")
     if beats == "device" and not device_beats:
         beats = "native"                               # a detector without the device stage: the host library
+    device_metrics = bool(metrics) and device_beats and hasattr(detector, "run_host_metrics")
     use_packed = bool(packed) and beats != "python" and hasattr(detector, "run_host_packed")
     bparams = None
     if beats and beats != "python":
@@ -234,13 +274,14 @@ def run_sharded(items: Sequence, params: dict, fs: Optional[int] = None, mode: s
     with ThreadPoolExecutor(host_threads) as ex:
         futs = []
         for idx in chunks:                             # the GPU runs chunk k+1 while host threads take chunk k
-            det_res = _detect_local(items, idx, fs, params, mode, detector, use_packed, device_beats, start_bpm_hint)
+            det_res = _detect_local(items, idx, fs, params, mode, detector, use_packed, device_beats, start_bpm_hint,
+                                    bool(metrics), device_metrics)
             per = max(1, len(idx) // host_threads)
             futs += [ex.submit(host_stage, idx[a:a + per], det_res) for a in range(0, len(idx), per)]
         for fu in futs:
             rows += fu.result()
     dev = detector.device if (dist.is_initialized() and dist.get_backend(group) == "nccl") else None
-    return gather_file_results(rows, len(items), group=group, device=dev)
+    return gather_file_results(rows, len(items), group=group, device=dev, metrics=bool(metrics))
 
 
 class FileResult:
@@ -253,6 +294,7 @@ class FileResult:
         self.final_peaks = np.zeros(0, np.int64) if final_peaks is None else np.asarray(final_peaks, np.int64)
         self.bpm_times = np.zeros(0) if bpm_times is None else np.asarray(bpm_times, np.float64)
         self.bpm = np.zeros(0) if bpm is None else np.asarray(bpm, np.float64)
+        self.record, self.n_hrv = None, 0              # run_sharded(metrics=True): metrics.record_of
 
     @classmethod
     def from_analysis(cls, index: int, raw_peaks, flags: int, a: dict) -> "FileResult":
@@ -265,13 +307,16 @@ class FileResult:
         return cls(index, raw_peaks, a["final_peaks"], times, curve, flags)
 
 
-def gather_file_results(rows: List[FileResult], n_items: int, group=None, device=None) -> Optional[List[dict]]:
+def gather_file_results(rows: List[FileResult], n_items: int, group=None, device=None,
+                        metrics: bool = False) -> Optional[List[dict]]:
     """The final result gather: every rank's records to rank 0 as
     one int64 slab [files, NMETA + raw peaks + final beats] and one f64 slab
     [files, 2 x BPM-curve points], padded to the widest over all ranks (the caps
     agreed by one all_reduce(MAX)); RCCL under the "nccl" backend (``device``:
-    this rank's GPU), gloo on CPU.  Errors travel as objects.  Returns the
-    records in item order on rank 0 (None elsewhere)."""
+    this rank's GPU), gloo on CPU.  Errors travel as objects.  ``metrics``:
+    the int64 slab ends in the HRV row count and the f64 slab in the 16-double
+    metrics record of each file.  Returns the records in item order on rank 0
+    (None elsewhere)."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -291,6 +336,12 @@ def gather_file_results(rows: List[FileResult], n_items: int, group=None, device
                             _pad_rows([x.final_peaks for x in rows], cf, -1, np.int64)], axis=1)
     fslab = np.concatenate([_pad_rows([x.bpm_times for x in rows], cb, np.nan, np.float64),
                             _pad_rows([x.bpm for x in rows], cb, np.nan, np.float64)], axis=1)
+    if metrics:
+        from ._native import METRICS_RECORD
+        nan = np.full(METRICS_RECORD, np.nan)
+        islab = np.concatenate([islab, np.asarray([x.n_hrv for x in rows], np.int64).reshape(nf, 1)], axis=1)
+        fslab = np.concatenate([fslab, np.asarray([nan if x.record is None else x.record for x in rows],
+                                                  np.float64).reshape(nf, METRICS_RECORD)], axis=1)
     ti = torch.from_numpy(np.ascontiguousarray(islab)).to(dev)
     tf = torch.from_numpy(np.ascontiguousarray(fslab)).to(dev)
     errors = {x.index: x.error for x in rows if x.error is not None}
@@ -309,7 +360,7 @@ def gather_file_results(rows: List[FileResult], n_items: int, group=None, device
     out: List[dict] = [None] * n_items
     for r, (si, sf) in enumerate(zip(gi, gf)):
         si, sf = si.cpu().numpy(), sf.cpu().numpy()
-        cb1 = sf.shape[1] // 2
+        cb1 = (sf.shape[1] - (METRICS_RECORD if metrics else 0)) // 2
         for row_i, row_f in zip(si, sf):
             i, npk, nfin, nb, flags = (int(x) for x in row_i[:NMETA])
             if i < 0:
@@ -320,4 +371,6 @@ def gather_file_results(rows: List[FileResult], n_items: int, group=None, device
             o = NMETA + cpf
             out[i] = {"raw_peaks": row_i[NMETA:NMETA + npk].copy(), "final_peaks": row_i[o:o + nfin].copy(),
                       "bpm_times": row_f[:nb].copy(), "bpm": row_f[cb1:cb1 + nb].copy(), "flags": flags, "rank": r}
+            if metrics:
+                out[i].update(metrics_record=row_f[2 * cb1:].copy(), n_hrv=int(row_i[-1]))
     return out

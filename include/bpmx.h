@@ -17,6 +17,8 @@
  *   bpmx_beats_device          <- bpm_analysis.py:1734-1757  analyze_wav_file stages 2-5 on
  *                                 those tables (_run_preliminary_pass, PeakClassifier,
  *                                 _refine_and_correct_peaks, calculate_bpm_series)
+ *   bpmx_metrics_device        <- bpm_analysis.py:1701-1722  _calculate_final_metrics on the beats and
+ *                                 the curve (HRV table, summary, HRR, slopes, inclines and declines)
  *   bpmx_synth / bpmx_synth_host   deterministic synthetic recordings (bench/tests)
  *
  * Plain C types only.  PCM and result arrays are DEVICE pointers (HBM); the
@@ -125,9 +127,12 @@ enum bpmx_option {
     BPMX_OPT_REF_NOSPLIT = 8192,     /* reference mode: gather every decimated sample first, then the forward
                                         pass inside k_envelope_ref, instead of forward-pass row chunks
                                         overlapping the next chunks' gather on a side stream (diagnostic) */
-    BPMX_OPT_BEATS_GLOBAL = 16384    /* bpmx_beats_device (set with bpmx_set_options): every recording's
+    BPMX_OPT_BEATS_GLOBAL = 16384,   /* bpmx_beats_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS for the tables that fit
                                         there (test/diagnostic) */
+    BPMX_OPT_METRICS_GLOBAL = 32768  /* bpmx_metrics_device (set with bpmx_set_options): every recording's
+                                        workspace in global memory, the curve and beats read where they lie
+                                        (test/diagnostic) */
 };
 
 /* bpmx_stats counters of the last run with BPMX_OPT_STATS */
@@ -324,8 +329,72 @@ int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_bea
                       double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
                       const bpmx_beats_out *out, void *stream);
 
+/* The final metrics on the device (bpmx_metrics_device).
+ *
+ * What the reference computes per file from the final beats and the curve
+ * (bpm_analysis.py:1701-1722 _calculate_final_metrics with :1414-1461 and
+ * :1486-1610): the windowed HRV table, the summary, heart-rate recovery, the
+ * steepest recovery and exertion slopes, the major inclines and declines.
+ * Computed from bpmx_beats_device's outputs where they lie; the arithmetic is
+ * csrc/bpmx_metrics_core.h, the same IEEE f64 operations in the same order as
+ * numpy, pandas and scipy apply them.  Timestamps are returned as positions
+ * into the file's curve (bpm_t / bpm), which the host indexes. */
+typedef struct {
+    int32_t hrv_window_size_beats, hrv_step_size_beats;   /* DEFAULT_PARAMS (:1414-1461), window >= 2, step >= 1 */
+    double min_duration_sec;    /* 10: find_major_hr_inclines / declines; the find_peaks distance is half of it */
+    double min_bpm_change;      /* 15 */
+    double prominence;          /* 5 (find_peaks) */
+    double slope_window_sec;    /* 20: peak recovery / exertion rate */
+    double hrr_interval_sec;    /* 60: calculate_hrr */
+} bpmx_metric_params;
+
+enum bpmx_metrics_status {      /* bpmx_metrics_out.status: 0, or the two bits below, or a negative code */
+    BPMX_METRICS_OK = 0,
+    BPMX_METRICS_TIE = 1,         /* the distance filter of find_peaks on the curve removed a candidate that no
+                                     strictly higher kept one covers: among equal heights the later index was
+                                     visited first (as for BPMX_F_*_TIE), numpy's argsort may differ */
+    BPMX_METRICS_E_DISTANCE = 2,  /* the find_peaks distance int(5 / mean step) is < 1: scipy raises ValueError;
+                                     no inclines or declines, everything else is written */
+    BPMX_METRICS_NONE = -18,      /* fewer than two final beats, or the file's beats status is not OK: counts
+                                     0, record NaN (the reference makes no metrics) */
+    BPMX_METRICS_OVERFLOW = -19   /* the file's slice reaches past cap_peaks: nothing written but the status */
+};
+
+/* bpmx_metrics_out.record: 16 doubles per file, NaN = absent.  Positions are
+ * indices into the file's curve. */
+enum bpmx_metrics_record {
+    BPMX_MR_AVG_BPM = 0, BPMX_MR_MIN_BPM = 1, BPMX_MR_MAX_BPM = 2, BPMX_MR_AVG_RMSSDC = 3, BPMX_MR_AVG_SDNN = 4,
+    BPMX_MR_HRR_PEAK = 5,           /* position of the maximum */
+    BPMX_MR_HRR_RECOVERY_BPM = 6, BPMX_MR_HRR_VALUE = 7,
+    BPMX_MR_RECOVERY = 8,           /* start position, end position, slope (BPM/s), duration (s) */
+    BPMX_MR_EXERTION = 12,          /* the same four */
+    BPMX_METRICS_RECORD = 16
+};
+
+typedef struct {            /* device; per-file slices start at pk_off[f] (rows and runs never outnumber raw peaks) */
+    double *hrv_time, *hrv_rmssdc, *hrv_sdnn, *hrv_bpm;   /* [cap_peaks] windowed HRV rows, n_hrv[f] valid */
+    int32_t *n_hrv;                                       /* [n_files] */
+    int32_t *inc_a, *inc_b, *dec_a, *dec_b;               /* [cap_peaks] curve positions of each run's start and
+                                                             end, in report order (steepest first) */
+    double *inc_slope, *inc_dur, *dec_slope, *dec_dur;    /* [cap_peaks] */
+    int32_t *n_inc, *n_dec;                               /* [n_files] */
+    double *record;                                       /* [n_files][BPMX_METRICS_RECORD] */
+    int32_t *status;                                      /* [n_files] bpmx_metrics_status */
+} bpmx_metrics_out;
+
+/* The final metrics of n_files recordings from `beats` (the outputs of
+ * bpmx_beats_device over `tables`: pk_off and cap_peaks are read from there),
+ * asynchronously on `stream`, ordered after the beat stages.  epoch_us: the
+ * origin of the curve's datetime index in microseconds since 1970 (the
+ * reference's datetime.fromtimestamp(0): 0 on a UTC machine).  Never
+ * synchronises the host; scratch comes from ctx.  Every pointer of `out` is
+ * required.  One workgroup per recording; see csrc/k_metrics.hip. */
+int bpmx_metrics_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_metric_params *params,
+                        int64_t epoch_us, const bpmx_packed *tables, const bpmx_beats_out *beats,
+                        const bpmx_metrics_out *out, void *stream);
+
 /* bpmx_option bits for the entry points that take no bpmx_params
- * (BPMX_OPT_BEATS_GLOBAL); they hold until set again. */
+ * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL); they hold until set again. */
 int bpmx_set_options(bpmx_ctx *ctx, int32_t options);
 
 /* Synthetic int16 recordings straight into HBM: file f gets seed seed0+f,
