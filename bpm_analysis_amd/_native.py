@@ -46,10 +46,18 @@ METRICS_OK, METRICS_TIE, METRICS_E_DISTANCE, METRICS_NONE, METRICS_OVERFLOW = 0,
 # bpmx_metrics_out.record (16 doubles per file, NaN = absent)
 MR_AVG_BPM, MR_MIN_BPM, MR_MAX_BPM, MR_AVG_RMSSDC, MR_AVG_SDNN = 0, 1, 2, 3, 4
 MR_HRR_PEAK, MR_HRR_RECOVERY_BPM, MR_HRR_VALUE, MR_RECOVERY, MR_EXERTION, METRICS_RECORD = 5, 6, 7, 8, 12, 16
+# bpmx_trace_out.record (bpmx_trace_field: 18 doubles per raw peak), .code (bpmx_trace_code) and .gap
+TR_BLEND, TR_BASE_CONF, TR_STAB_FACTOR, TR_STAB_RATIO, TR_ADJ_AMOUNT, TR_ADJ_RATIO, TR_ADJ_RMAX = 0, 1, 2, 3, 4, 5, 6
+TR_IV_AMOUNT, TR_IV_GAP, TR_IV_CAP, TR_FINAL = 7, 8, 9, 10
+TR_L_RHYTHM, TR_L_RR, TR_L_EXPECTED, TR_L_AMP, TR_L_RATIO, TR_L_CONF, TR_L_IMPLIED, TR_NFIELDS = 11, 12, 13, 14, 15, 16, 17, 18
+TR_S1_PAIRED, TR_S2_PAIRED, TR_LONE_VALID, TR_FIRST_BEAT, TR_LAST_PEAK, TR_CASCADE, TR_NOISE, TR_OUTCOME = 1, 2, 3, 4, 5, 6, 7, 15
+TRF_STABILITY, TRF_PENALIZED, TRF_BOOSTED, TRF_INTERVAL, TRF_FORWARD = 16, 32, 64, 128, 256
+TR_GAP_NONE, TR_GAP_S1, TR_GAP_S2 = 0, 1, 2
 
 EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy", "bpmx_decimated_length",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
-           "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device"]
+           "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
+           "bpmx_beats_device_ex", "bpmx_pack_trough_floor"]
 
 
 class Params(ctypes.Structure):
@@ -98,6 +106,13 @@ class BeatsOut(ctypes.Structure):
     _fields_ = [("final_idx", ctypes.c_void_p), ("n_final", ctypes.c_void_p), ("bpm_t", ctypes.c_void_p),
                 ("bpm", ctypes.c_void_p), ("n_bpm", ctypes.c_void_p), ("pass_", ctypes.c_void_p),
                 ("tags", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class TraceOut(ctypes.Structure):
+    """bpmx_trace_out: the device arrays of the decision trace
+    bpmx_beats_device_ex fills (per-file slices at pk_off[f]; every pointer
+    required)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("record", "code", "lt_pos", "lt_bpm", "n_lt", "dev_t", "dev", "gap")]
 
 
 class MetricParams(ctypes.Structure):
@@ -197,6 +212,15 @@ def load() -> ctypes.CDLL:
         L.bpmx_metrics_device.argtypes = [P, I32, I32, ctypes.POINTER(MetricParams), I64, ctypes.POINTER(PackedOut),
                                           ctypes.POINTER(BeatsOut), ctypes.POINTER(MetricsOut), P]
         L.bpmx_metrics_device.restype = ctypes.c_int
+    if hasattr(L, "bpmx_beats_device_ex"):
+        from ._host import BeatParams
+        L.bpmx_beats_device_ex.argtypes = [P, I32, I32, ctypes.POINTER(BeatParams), ctypes.c_double,
+                                           ctypes.POINTER(PackedOut), P, ctypes.POINTER(BeatsOut), P,
+                                           ctypes.POINTER(TraceOut), P]
+        L.bpmx_beats_device_ex.restype = ctypes.c_int
+        L.bpmx_pack_trough_floor.argtypes = [P, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_int64), I32, I32,
+                                             ctypes.POINTER(PackedOut), P, P]
+        L.bpmx_pack_trough_floor.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

@@ -1,7 +1,8 @@
 /*
  * bpmx_api.hip — host side of the C ABI (include/bpmx.h): context, scratch,
- * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack and
- * bpmx_beats_device.
+ * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
+ * bpmx_pack_trough_floor, bpmx_beats_device, bpmx_beats_device_ex and
+ * bpmx_metrics_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -64,7 +65,7 @@ int beats_cap(int64_t n_frames, int32_t fs) {
 
 /* the beat stages over the peak table: one launch sized by the plan; the
  * global workspace (recordings beyond the LDS budget) is context scratch */
-int beats_stage(bpmx_ctx *ctx, const BeatsPlan &B, BeatsArgs &a, hipStream_t s) {
+int beats_stage(bpmx_ctx *ctx, const BeatsPlan &B, BeatsArgs &a, hipStream_t s, const BeatsExArgs *ex = nullptr) {
     int rc = BPMX_OK;
     a.lds_n = B.lds_n;
     a.gws = nullptr;
@@ -72,7 +73,13 @@ int beats_stage(bpmx_ctx *ctx, const BeatsPlan &B, BeatsArgs &a, hipStream_t s) 
         a.gws = (unsigned char *)ctx->buf("beats_ws", B.gws, &rc);
         if (rc != BPMX_OK) return rc;
     }
-    LAUNCH(ctx, s, "k_beats", k_beats, dim3(B.grid), dim3(BEATS_T), B.lds, s, a);
+    if (!ex) {
+        LAUNCH(ctx, s, "k_beats", k_beats, dim3(B.grid), dim3(BEATS_T), B.lds, s, a);
+    } else if (ex->record) {
+        LAUNCH(ctx, s, "k_beats_trace", k_beats_trace, dim3(B.grid), dim3(BEATS_T), B.lds, s, a, *ex);
+    } else {
+        LAUNCH(ctx, s, "k_beats_hints", k_beats_hints, dim3(B.grid), dim3(BEATS_T), B.lds, s, a, *ex);
+    }
     return BPMX_OK;
 }
 
@@ -501,17 +508,23 @@ int bpmx_set_options(bpmx_ctx *ctx, int32_t options) {
     return BPMX_OK;
 }
 
-int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
-                      double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
-                      const bpmx_beats_out *out, void *stream) {
-    if (!ctx || !params || !in || !out) return fail(BPMX_E_ARG, "bpmx_beats_device: NULL argument");
-    if (n_files < 1 || sr < 1) return fail(BPMX_E_ARG, "bpmx_beats_device: bad n_files/sr");
+namespace {
+/* bpmx_beats_device and bpmx_beats_device_ex (`who` names the caller in the messages) */
+int beats_device(const char *who, bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
+                 double start_bpm_hint, const bpmx_packed *in, const int32_t *flags, const bpmx_beats_out *out,
+                 const double *hints, const bpmx_trace_out *trace, void *stream) {
+    const std::string w(who);
+    if (!ctx || !params || !in || !out) return fail(BPMX_E_ARG, w + ": NULL argument");
+    if (n_files < 1 || sr < 1) return fail(BPMX_E_ARG, w + ": bad n_files/sr");
     if (!in->pk_off || !in->pk_idx || !in->pk_env || !in->pk_floor || in->cap_peaks < 0 ||
         in->cap_peaks >= (int64_t)INT_MAX)
-        return fail(BPMX_E_ARG, "bpmx_beats_device: needs the peak table (pk_off, pk_idx, pk_env, pk_floor) and "
-                                "0 <= cap_peaks < 2^31");
+        return fail(BPMX_E_ARG, w + ": needs the peak table (pk_off, pk_idx, pk_env, pk_floor) and "
+                                    "0 <= cap_peaks < 2^31");
     if (!out->final_idx || !out->n_final || !out->bpm_t || !out->bpm || !out->n_bpm || !out->status)
-        return fail(BPMX_E_ARG, "bpmx_beats_device: final_idx, n_final, bpm_t, bpm, n_bpm and status are required");
+        return fail(BPMX_E_ARG, w + ": final_idx, n_final, bpm_t, bpm, n_bpm and status are required");
+    if (trace && (!trace->record || !trace->code || !trace->lt_pos || !trace->lt_bpm || !trace->n_lt ||
+                  !trace->dev_t || !trace->dev || !trace->gap))
+        return fail(BPMX_E_ARG, w + ": every pointer of bpmx_trace_out is required");
     HIP_TRY(hipSetDevice(ctx->device));
     BeatsArgs a{};
     a.n_files = n_files; a.sr = sr; a.cap = in->cap_peaks;
@@ -519,7 +532,66 @@ int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_bea
     a.flags = flags; a.hint = start_bpm_hint; a.P = *params;
     a.final_idx = out->final_idx; a.n_final = out->n_final; a.bpm_t = out->bpm_t; a.bpm = out->bpm;
     a.n_bpm = out->n_bpm; a.pass = out->pass; a.tags = out->tags; a.status = out->status;
-    return beats_stage(ctx, beats_plan(n_files, in->cap_peaks, ctx->options), a, (hipStream_t)stream);
+    const BeatsPlan plan = beats_plan(n_files, in->cap_peaks, ctx->options);
+    if (!hints && !trace) return beats_stage(ctx, plan, a, (hipStream_t)stream);
+    BeatsExArgs e{};
+    e.hints = hints;
+    if (trace) {
+        e.record = trace->record; e.code = trace->code; e.lt_pos = trace->lt_pos; e.lt_bpm = trace->lt_bpm;
+        e.n_lt = trace->n_lt; e.dev_t = trace->dev_t; e.dev = trace->dev; e.gap = trace->gap;
+    }
+    return beats_stage(ctx, plan, a, (hipStream_t)stream, &e);
+}
+}  // namespace
+
+int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
+                      double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
+                      const bpmx_beats_out *out, void *stream) {
+    return beats_device("bpmx_beats_device", ctx, n_files, sr, params, start_bpm_hint, in, flags, out, nullptr,
+                        nullptr, stream);
+}
+
+int bpmx_beats_device_ex(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
+                         double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
+                         const bpmx_beats_out *out, const double *hints, const bpmx_trace_out *trace,
+                         void *stream) {
+    return beats_device("bpmx_beats_device_ex", ctx, n_files, sr, params, start_bpm_hint, in, flags, out, hints,
+                        trace, stream);
+}
+
+int bpmx_pack_trough_floor(bpmx_ctx *ctx, const bpmx_out *in, const int64_t *frame_offsets, int32_t n_files,
+                           int32_t ds, const bpmx_packed *tables, double *tr_floor, void *stream) {
+    if (!ctx || !in || !frame_offsets || !tables || !tr_floor)
+        return fail(BPMX_E_ARG, "bpmx_pack_trough_floor: NULL argument");
+    if (n_files < 1 || ds < 1) return fail(BPMX_E_ARG, "bpmx_pack_trough_floor: bad n_files/ds");
+    if (!in->floor || !tables->tr_off || !tables->tr_idx || tables->cap_troughs < 0)
+        return fail(BPMX_E_ARG, "bpmx_pack_trough_floor: needs floor and the trough table (tr_off, tr_idx, "
+                                "cap_troughs >= 0)");
+    std::vector<int64_t> doff((size_t)n_files + 1);
+    doff[0] = 0;
+    for (int f = 0; f < n_files; ++f) {
+        const int64_t n = frame_offsets[f + 1] - frame_offsets[f];
+        if (n < 0) return fail(BPMX_E_ARG, "frame offsets must be non-decreasing");
+        const int64_t nd = bpmx_decimated_length(n, ds);
+        if (nd >= (int64_t)INT_MAX / 2) return fail(BPMX_E_LIMIT, "recording too long");
+        doff[f + 1] = doff[f] + nd;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = BPMX_OK;
+    bool grew = false;
+    /* bpmx_pack's offsets buffer and its key: behind the pack of the same batch nothing is copied */
+    int64_t *d_doff = (int64_t *)ctx->buf("pack_geo", doff.size() * 8, &rc, &grew);
+    if (rc != BPMX_OK) return rc;
+    if (grew || doff != ctx->pack_key) {
+        ctx->pack_key.swap(doff);
+        HIP_TRY(hipMemcpyAsync(d_doff, ctx->pack_key.data(), ctx->pack_key.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    TroughFloorArgs a{};
+    a.doff = d_doff; a.tr_off = tables->tr_off; a.tr_idx = tables->tr_idx; a.floor = in->floor;
+    a.cap = tables->cap_troughs; a.out = tr_floor;
+    LAUNCH(ctx, s, "k_pack_trough_floor", k_pack_trough_floor, dim3(n_files), dim3(PK_GATHER_T), 0, s, a);
+    return BPMX_OK;
 }
 
 int bpmx_metrics_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_metric_params *params,

@@ -46,6 +46,7 @@
 #include <stdint.h>
 
 #include "../../include/bpmx_host.h"
+#include "../../include/bpmx.h" /* bpmx_trace_field, bpmx_trace_code: the layout of the decision trace */
 
 #if defined(__HIPCC__)
 #define BPMX_HD __host__ __device__
@@ -306,6 +307,50 @@ BPMX_HD inline void beats_sort(const X &x, double *a, int64_t n) {
 /* ---- the classifier ------------------------------------------------------ */
 enum { BT_NONE = 0, BT_S1 = 1, BT_S2 = 2, BT_LONE = 3, BT_NOISE = 4 };
 
+/* ---- the decision trace (optional) --------------------------------------- */
+/* What the main classification pass and the gap fill decide, kept for the
+ * reference's per-peak debug strings (beats.PeakClassifier._pair / ._lone,
+ * fix_rhythmic_discontinuities): a trace sink T is a policy of the functions
+ * below.  bc_notrace (the default) has on == 0 and empty members, so every
+ * `if (T::on)` block falls away and the instantiation is the code without a
+ * trace.  beats_trace stores into one recording's slices (all at pk_off[f]):
+ *   rec   f64[n][BPMX_TR_NFIELDS]  the values a peak's strings format; only the
+ *                                  fields its code announces are written
+ *   code  i32[n]   BPMX_TR_* outcome | BPMX_TRF_* optional lines
+ *   lt_pos / lt_bpm [n_lt]  after every classifier iteration with a beat: the
+ *                                  table position of the last beat, the belief
+ *   dev_t / dev [n - 1]     the main pass' smoothed deviation series
+ *   gap   i32[n]   the label pass `it` of the gap fill gave the peak in bits
+ *                  2 it .. 2 it + 1 (BPMX_TR_GAP_*)
+ * The serial parts store from lane 0 where they decide; dev_t, dev and the
+ * zeroes of gap are written by all lanes. */
+struct bc_notrace {
+    enum { on = 0 };
+    BPMX_HD void put(int64_t, int, double) const {}
+    BPMX_HD void code_at(int64_t, int32_t) const {}
+    BPMX_HD void belief(int64_t, int32_t, double) const {}
+    BPMX_HD void beliefs(int64_t) const {}
+    BPMX_HD void gap_label(int64_t, int, int) const {}
+    BPMX_HD void gap_clear(int64_t) const {}
+    BPMX_HD void deviation(int64_t, double, double) const {}
+};
+struct beats_trace {
+    enum { on = 1 };
+    double *rec;
+    int32_t *code, *lt_pos;
+    double *lt_bpm;
+    int32_t *n_lt;                                    /* this recording's count */
+    double *dev_t, *dev;
+    int32_t *gap;
+    BPMX_HD void put(int64_t j, int field, double v) const { rec[j * BPMX_TR_NFIELDS + field] = v; }
+    BPMX_HD void code_at(int64_t j, int32_t v) const { code[j] = v; }
+    BPMX_HD void belief(int64_t k, int32_t pos, double bpm) const { lt_pos[k] = pos; lt_bpm[k] = bpm; }
+    BPMX_HD void beliefs(int64_t k) const { *n_lt = (int32_t)k; }
+    BPMX_HD void gap_label(int64_t j, int it, int label) const { gap[j] |= label << (2 * it); }
+    BPMX_HD void gap_clear(int64_t j) const { gap[j] = 0; }
+    BPMX_HD void deviation(int64_t i, double t, double v) const { dev_t[i] = t; dev[i] = v; }
+};
+
 /* strength, the smoothed deviation series and its times (PeakClassifier's
  * constructor): gathers on all lanes, the Kahan rolling mean on lane 0 */
 template <class X>
@@ -353,15 +398,21 @@ BPMX_HD inline double bc_dev_asof(const bc_cls &c, double t) {
     return k >= 0 ? c.dev[k] : bc_nan();
 }
 
+/* *flags: the BPMX_TRF_* lines the attempt has (written with a trace only) */
+template <class T = bc_notrace>
 BPMX_HD inline bool bc_pair(const bc_cls &c, const bpmx_beat_params &p, int64_t j, double ratio, double ltb,
-                            int64_t n_beats) {
+                            int64_t n_beats, const T &tr = T(), int32_t *flags = nullptr) {
+    int32_t fl = 0;
     const int64_t s1 = c.idx[j], s2 = c.idx[j + 1];
     const int32_t sr = c.sr;
     const double gap = (double)(s2 - s1) / (double)sr;
     double conf = blended_confidence(bc_dev_asof(c, (double)s1 / (double)sr), ltb, p);
+    if (T::on) { tr.put(j, BPMX_TR_BLEND, blend(ltb, p)); tr.put(j, BPMX_TR_BASE_CONF, conf); }
     if (n_beats >= 5) {
         const double xs[2] = {0.0, 1.0}, ys[2] = {p.stability_confidence_floor, p.stability_confidence_ceiling};
-        conf *= interp1(ratio, xs, ys);
+        const double sf = interp1(ratio, xs, ys);
+        conf *= sf;
+        if (T::on) { fl |= BPMX_TRF_STABILITY; tr.put(j, BPMX_TR_STAB_FACTOR, sf); tr.put(j, BPMX_TR_STAB_RATIO, ratio); }
     }
     const double a1 = c.str[j], a2 = c.str[j + 1];
     const double r21 = a2 / (a1 + 1e-9);
@@ -375,11 +426,16 @@ BPMX_HD inline bool bc_pair(const bc_cls &c, const bpmx_beat_params &p, int64_t 
         const double amt = p.penalty_amount_min + clipv((r21 / r_max - 1.0) / 2.0, 0, 1) *
                                                       (p.penalty_amount_max - p.penalty_amount_min);
         conf -= amt;
+        if (T::on) {
+            fl |= BPMX_TRF_PENALIZED;
+            tr.put(j, BPMX_TR_ADJ_AMOUNT, amt); tr.put(j, BPMX_TR_ADJ_RATIO, r21); tr.put(j, BPMX_TR_ADJ_RMAX, r_max);
+        }
     } else if (a1 > a2 * boost_at) {
         const double r12 = a1 / (a2 + 1e-9);
         const double amt = p.boost_amount_min + clipv((r12 - boost_at) / (4.0 - boost_at), 0, 1) *
                                                     (p.boost_amount_max - p.boost_amount_min);
         conf += amt;
+        if (T::on) { fl |= BPMX_TRF_BOOSTED; tr.put(j, BPMX_TR_ADJ_AMOUNT, amt); tr.put(j, BPMX_TR_ADJ_RATIO, r12); }
     }
     conf = py_max(0.0, py_min(1.0, conf));
     const double cap = py_min(p.s1_s2_interval_cap_sec, (60.0 / ltb) * p.s1_s2_interval_rr_fraction);
@@ -388,14 +444,20 @@ BPMX_HD inline bool bc_pair(const bc_cls &c, const bpmx_beat_params &p, int64_t 
         if (gap > z0) {
             const double amt = clipv((gap - z0) / (z1 - z0 + 1e-9), 0, 1) * p.interval_max_penalty;
             conf = py_max(0, conf - amt);
+            if (T::on) {
+                fl |= BPMX_TRF_INTERVAL;
+                tr.put(j, BPMX_TR_IV_AMOUNT, amt); tr.put(j, BPMX_TR_IV_GAP, gap); tr.put(j, BPMX_TR_IV_CAP, cap);
+            }
         }
     }
+    if (T::on) { tr.put(j, BPMX_TR_FINAL, conf); *flags = fl; }
     return conf >= c.thr;
 }
 
 /* (valid, rejected on rhythm) */
+template <class T = bc_notrace>
 BPMX_HD inline void bc_lone(const bc_cls &c, const bpmx_beat_params &p, int64_t j, int64_t jl, double ltb,
-                            bool &valid, bool &on_rhythm) {
+                            bool &valid, bool &on_rhythm, const T &tr = T()) {
     const double RHYTHM_X[4] = {0.0, 0.15, 0.30, 0.50}, RHYTHM_Y[4] = {1.0, 0.8, 0.4, 0.0};
     const double AMP_X[4] = {0.0, 0.4, 0.7, 1.0}, AMP_Y[4] = {0.0, 0.4, 0.8, 1.0};
     const int64_t cur = c.idx[j], last = c.idx[jl];
@@ -406,12 +468,17 @@ BPMX_HD inline void bc_lone(const bc_cls &c, const bpmx_beat_params &p, int64_t 
     const double ar = c.str[j] / (c.str[jl] + 1e-9);
     const double am = interp1(ar, AMP_X, AMP_Y);
     const double conf = (rs * p.lone_s1_rhythm_weight) + (am * p.lone_s1_amplitude_weight);
+    if (T::on) {
+        tr.put(j, BPMX_TR_L_RHYTHM, rs); tr.put(j, BPMX_TR_L_RR, rr); tr.put(j, BPMX_TR_L_EXPECTED, exp_rr);
+        tr.put(j, BPMX_TR_L_AMP, am); tr.put(j, BPMX_TR_L_RATIO, ar); tr.put(j, BPMX_TR_L_CONF, conf);
+    }
     if (conf < p.lone_s1_confidence_threshold) { valid = false; on_rhythm = true; return; }
     on_rhythm = false;
     if (j < c.n - 1) {
         const double fwd = (double)((int64_t)c.idx[j + 1] - cur) / (double)sr;
         if (fwd < exp_rr * p.lone_s1_forward_check_pct && !(c.envpk[j] > (c.envpk[j + 1] * 1.7))) {
             valid = false;
+            if (T::on) tr.put(j, BPMX_TR_L_IMPLIED, fwd > 0 ? 60.0 / fwd : (double)INFINITY);
             return;
         }
     }
@@ -420,11 +487,15 @@ BPMX_HD inline void bc_lone(const bc_cls &c, const bpmx_beat_params &p, int64_t 
 
 /* classify_peaks on one lane: the beats as table positions (ascending) into
  * `beats`, one tag per raw peak; returns the number of beats */
+template <class T = bc_notrace>
 BPMX_HD inline int64_t bc_classify(const bc_cls &c, const bpmx_beat_params &p, double start_bpm, int32_t *beats,
-                                   int8_t *paired, int8_t *tag) {
+                                   int8_t *paired, int8_t *tag, const T &tr = T()) {
     const int64_t n = c.n;
     for (int64_t i = 0; i < n; ++i) tag[i] = BT_NONE;
+    int64_t n_lt = 0;
+    int32_t fl = 0;
     if (n < 2) {
+        if (T::on) tr.beliefs(0);
         for (int64_t i = 0; i < n; ++i) beats[i] = (int32_t)i;
         return n;
     }
@@ -439,29 +510,35 @@ BPMX_HD inline int64_t bc_classify(const bc_cls &c, const bpmx_beat_params &p, d
         if (j >= n - 1) {
             add = j;
             tag[j] = BT_LONE;
+            if (T::on) tr.code_at(j, BPMX_TR_LAST_PEAK);
             j += 1;
-        } else if (bc_pair(c, p, j, ratio, ltb, nb)) {
+        } else if (bc_pair(c, p, j, ratio, ltb, nb, tr, &fl)) {
             add = j;
             is_pair = true;
             tag[j] = BT_S1;
             tag[j + 1] = BT_S2;
+            if (T::on) { tr.code_at(j, BPMX_TR_S1_PAIRED | fl); tr.code_at(j + 1, BPMX_TR_S2_PAIRED); }
             rr_fails = 0;
             j += 2;
         } else {
             bool valid = true, on_rhythm = false;
-            if (nb > 0) bc_lone(c, p, j, beats[nb - 1], ltb, valid, on_rhythm);
+            if (nb > 0) bc_lone(c, p, j, beats[nb - 1], ltb, valid, on_rhythm, tr);
             if (valid) {
                 add = j;
                 tag[j] = BT_LONE;
                 rr_fails = 0;
+                if (T::on) tr.code_at(j, (nb > 0 ? BPMX_TR_LONE_VALID : BPMX_TR_FIRST_BEAT) | fl);
             } else {
                 rr_fails = on_rhythm ? rr_fails + 1 : 0;
+                const int32_t rej = on_rhythm ? 0 : BPMX_TRF_FORWARD;
                 if (rr_fails >= p.cascade_reset_trigger_count) {
                     add = j;
                     tag[j] = BT_LONE;
                     rr_fails = 0;
+                    if (T::on) tr.code_at(j, BPMX_TR_CASCADE | rej | fl);
                 } else {
                     tag[j] = BT_NOISE;
+                    if (T::on) tr.code_at(j, BPMX_TR_NOISE | rej | fl);
                 }
             }
             j += 1;
@@ -480,7 +557,9 @@ BPMX_HD inline int64_t bc_classify(const bc_cls &c, const bpmx_beat_params &p, d
             const double rr = (double)((int64_t)c.idx[beats[nb - 1]] - (int64_t)c.idx[beats[nb - 2]]) / (double)c.sr;
             if (rr > 0) ltb = update_long_term_bpm(rr, ltb, p);
         }
+        if (T::on && nb > 0) { tr.belief(n_lt, beats[nb - 1], ltb); ++n_lt; }
     }
+    if (T::on) tr.beliefs(n_lt);
     return nb;
 }
 
@@ -578,10 +657,11 @@ BPMX_HD inline int64_t beats_correct_by_rhythm(const X &x, int64_t ns1, const in
 /* one gap-fill + short-interval pass over the beats in I0 (count *ns1, in
  * place); a raw peak counts as noisy when its tag is Noise (a gap correction
  * keeps it so).  Returns the number of corrections. */
-template <class X>
+template <class X, class T = bc_notrace>
 BPMX_HD inline int beats_fix_discontinuities(const X &x, int64_t *ns1, int64_t n, const int32_t *idx,
                                              const double *env, const double *flo, int32_t sr,
-                                             const bpmx_beat_params &p, const beats_ws &w) {
+                                             const bpmx_beat_params &p, const beats_ws &w, int it = 0,
+                                             const T &tr = T()) {
     const int64_t m = 3, cnt = *ns1;
     if (cnt < 2 * m) return 0;
     int32_t *s1 = w.I[0], *added = w.I[1], *merged = w.I[2];
@@ -621,6 +701,7 @@ BPMX_HD inline int beats_fix_discontinuities(const X &x, int64_t *ns1, int64_t n
                     if (py_max(0, ex) > waiver * flo[k] && (env[k + 1] / (env[k] + 1e-9)) < max_ratio) {
                         n_fix += 1;
                         added[na++] = (int32_t)k;
+                        if (T::on) { tr.gap_label(k, it, BPMX_TR_GAP_S1); tr.gap_label(k + 1, it, BPMX_TR_GAP_S2); }
                         break;
                     }
                 }
@@ -662,11 +743,11 @@ BPMX_HD inline int beats_fix_discontinuities(const X &x, int64_t *ns1, int64_t n
  * bpm[n], pass_out[3] and tags_out[n] optional.  Returns BPMX_HOST_OK or
  * BPMX_HOST_E_FEW_PEAKS (every lane the same value).  The workspace `w` holds
  * beats_ws_bytes(n, .) bytes; idx / env may point into it (staged copies). */
-template <class X>
+template <class X, class T = bc_notrace>
 BPMX_HD inline int beats_core(const X &x, int64_t n, const int32_t *idx, const double *env, const double *flo,
                               int32_t sr, const bpmx_beat_params &p, double hint, const beats_ws &w,
                               int32_t *final_out, int32_t *n_final, double *bpm_t_out, double *bpm_out,
-                              int32_t *n_bpm, double *pass_out, int8_t *tags_out) {
+                              int32_t *n_bpm, double *pass_out, int8_t *tags_out, const T &tr = T()) {
     const bool have_hint = hint == hint;
     const bool lead = x.lane() == 0;
     if (lead) { *n_final = 0; *n_bpm = 0; }
@@ -719,15 +800,20 @@ BPMX_HD inline int beats_core(const X &x, int64_t n, const int32_t *idx, const d
     if (lead) {
         c.thr = p.pairing_confidence_threshold;
         c.have_rec = w.hi[BH_REC] != 0; c.t_pk = w.hd[BH_TPK]; c.t_end = w.hd[BH_TEND];
-        w.hi[BH_NS1] = (int32_t)bc_classify(c, p, w.hd[BH_START], w.I[0], w.paired, w.tag);
+        w.hi[BH_NS1] = (int32_t)bc_classify(c, p, w.hd[BH_START], w.I[0], w.paired, w.tag, tr);
     }
     x.sync();
     if (tags_out) BPMX_PAR_FOR(x, i, n) tags_out[i] = w.tag[i];
+    if (T::on && n >= 2) {                            /* before the refinement reuses S1 / S2 */
+        BPMX_PAR_FOR(x, i, n - 1) tr.deviation(i, w.S[2][i], w.S[1][i]);
+        BPMX_PAR_FOR(x, i, n) tr.gap_clear(i);
+        x.sync();
+    }
     if (n < 2) return BPMX_HOST_E_FEW_PEAKS;          /* the reference's refinement raises KeyError here */
     /* refinement (:1655-1698) */
     int64_t nf = beats_correct_by_rhythm(x, w.hi[BH_NS1], idx, env, sr, p, w);
     for (int it = 0; it < 5; ++it)
-        if (beats_fix_discontinuities(x, &nf, n, idx, env, flo, sr, p, w) == 0) break;
+        if (beats_fix_discontinuities(x, &nf, n, idx, env, flo, sr, p, w, it, tr) == 0) break;
     BPMX_PAR_FOR(x, i, nf) final_out[i] = idx[w.I[0][i]];
     if (lead) *n_final = (int32_t)nf;
     /* final BPM curve (:1463-1484), only when >= 2 beats survive (:1749-1757) */

@@ -528,6 +528,27 @@ struct BeatsArgs {
     bpmx_beat_params P;
 };
 __global__ void k_beats(BeatsArgs A);
+/* bpmx_beats_device_ex: what it adds to BeatsArgs, kept apart so that k_beats
+ * and its arguments stay as they are */
+struct BeatsExArgs {
+    const double *hints;        /* optional [F], NaN = None; null: BeatsArgs.hint for every recording */
+    double *record;             /* the decision trace (bpmx_trace_out), slices at pk_off[f]; k_beats_trace only */
+    int32_t *code, *lt_pos, *n_lt, *gap;
+    double *lt_bpm, *dev_t, *dev;
+};
+__global__ void k_beats_hints(BeatsArgs A, BeatsExArgs E);   /* per-file hints, no trace */
+__global__ void k_beats_trace(BeatsArgs A, BeatsExArgs E);   /* per-file hints (optional) and the trace */
+
+/* bpmx_pack_trough_floor (k_pack.hip): the floor at the troughs of a packed table */
+struct TroughFloorArgs {
+    const int64_t *doff;        /* [F+1] decimated offsets */
+    const int64_t *tr_off;      /* [F+1] */
+    const int32_t *tr_idx;
+    const double *floor;
+    int64_t cap;
+    double *out;
+};
+__global__ void k_pack_trough_floor(TroughFloorArgs A);
 
 /* bpmx_metrics_device (k_metrics.hip): one workgroup of METRICS_T threads per recording */
 enum { METRICS_T = 256 };

@@ -8,6 +8,8 @@
  *   k_pack_gather   per (file, table) one workgroup: index, env and floor at
  *                   each peak / trough, copied as bit patterns; entries whose
  *                   table position is at or beyond the capacity are dropped
+ *   k_pack_trough_floor  bpmx_pack_trough_floor: the floor at the packed
+ *                   troughs, from the table's own offsets and indices
  *   k_y16_max       per file max|y|: |y| bit patterns order as unsigned
  *                   integers and every NaN pattern lies above inf, so a 64-bit
  *                   atomic maximum of the bits propagates a NaN by itself
@@ -79,6 +81,24 @@ __global__ __launch_bounds__(PK_GATHER_T) void k_pack_gather(PackArgs A) {
         A.oidx[w][j] = (int32_t)i;
         oenv[j] = in ? env[i] : QNAN_BITS;
         if (oflo) oflo[j] = in ? flo[i] : QNAN_BITS;
+    }
+}
+
+/* tr_floor[j] = floor[D_f + tr_idx[j]] as bit patterns, per file one
+ * workgroup; the slice is clipped to the capacity, an index outside the
+ * recording reads nothing */
+__global__ __launch_bounds__(PK_GATHER_T) void k_pack_trough_floor(TroughFloorArgs A) {
+    const int64_t f = blockIdx.x;
+    const int64_t D = A.doff[f], nd = A.doff[f + 1] - D;
+    const int64_t o = A.tr_off[f];
+    int64_t e = A.tr_off[f + 1];
+    if (o < 0) return;
+    if (e > A.cap) e = A.cap;
+    const u64 *flo = (const u64 *)A.floor + D;
+    u64 *out = (u64 *)A.out;
+    for (int64_t j = o + threadIdx.x; j < e; j += PK_GATHER_T) {
+        const int64_t i = A.tr_idx[j];
+        out[j] = (i >= 0 && i < nd) ? flo[i] : QNAN_BITS;
     }
 }
 

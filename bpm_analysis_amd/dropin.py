@@ -295,6 +295,86 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
     return out
 
 
+def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output_directory: str,
+                                 start_bpm_hints: Sequence = None, original_file_paths: Sequence[str] = None,
+                                 mode: str = None, device: int = 0) -> List[dict]:
+    """``beats.analyze_wav_file`` for many WAV files with every stage on the
+    device: per file ``<base>_bpm_plot.csv``, ``<base>_Analysis_Summary.md``,
+    ``<base>_Debug_Log.md`` and ``<base>_Analysis_Settings.json`` (and both
+    debug WAVs with ``params["save_filtered_wav"]``), byte for byte what
+    ``analyze_wav_file`` writes apart from the markdown files' timestamp line.
+    The plot (``<base>_bpm_plot.html``) needs whole envelopes and is not made.
+
+    Files are read and grouped as ``analyze_wav_files`` does; each group is one
+    ``Detector.run_host_reports``: hot path, tables, beat stages with one start
+    hint per file and the decision trace, final metrics, all on the GPU, and
+    ``explain`` + ``reports.write_reports_packed`` on the host.  No
+    ``beats.PeakClassifier`` runs.  A file whose metrics met a decisive
+    find_peaks tie or an invalid distance has them recomputed on the host
+    (``Metrics.to_host``).  ``start_bpm_hints``: one per file (None = none);
+    ``original_file_paths`` name the reports (default: ``file_paths``).
+
+    Returns one dict per path, in order: ``run_host_reports``' dict, or
+    ``error`` with the exception the reference raises for that file; as there,
+    a file with fewer than two final beats gets no reports
+    (``final_metrics`` None)."""
+    from .reports import write_reports_packed
+    if mode is None:
+        mode = params.get("bpmx_mode", "reference")
+    n = len(file_paths)
+    hints = [None] * n if start_bpm_hints is None else list(start_bpm_hints)
+    names = list(file_paths) if original_file_paths is None else list(original_file_paths)
+    if len(hints) != n or len(names) != n:
+        raise ValueError("start_bpm_hints and original_file_paths need one entry per file")
+    save = bool(params.get("save_filtered_wav", False))
+    out: List[dict] = [None] * n
+    groups: Dict[tuple, List[int]] = {}
+    audio = []
+    for k, path in enumerate(file_paths):
+        try:
+            fs, a = _read_wav(path)
+        except Exception as exc:                      # wavfile errors propagate per file, as in the GUI loop
+            out[k] = {"error": exc}
+            audio.append(None)
+            continue
+        audio.append((fs, a))
+        groups.setdefault((fs, a.dtype.str, 1 if a.ndim == 1 else a.shape[1]), []).append(k)
+    det = default_detector(device)
+    for (fs, _, _), idx in groups.items():
+        try:
+            d = design(fs, params)                    # clamp warnings / Nyquist ValueError, once per group
+        except ValueError as exc:
+            for k in idx:
+                out[k] = {"error": exc}
+            continue
+        try:
+            if d.distance < 1:
+                raise ValueError(DISTANCE_MSG)
+            res = det.run_host_reports([audio[k][1] for k in idx], fs, params, mode=mode,
+                                       hints=[hints[k] for k in idx])
+        except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
+            if isinstance(exc, N.BpmxError) and not exc.per_file:
+                raise                                 # HIP / device failure: not a per-file error
+            for k in idx:                             # (a too-short file fails first, in filtfilt)
+                short = -(-audio[k][1].shape[0] // d.ds) <= 15
+                out[k] = {"error": ValueError(PADLEN_MSG) if short else exc}
+            continue
+        for k, r in zip(idx, res):
+            err = _file_error(r["flags"], params, d.sr)
+            if err is not None:
+                out[k] = {"error": err}
+                continue
+            if save:
+                _write_debug_wavs(file_paths[k], output_directory, d.sr, r["y16"])
+            if "error" in r:                          # < 2 raw peaks (KeyError), scipy's ValueError in the metrics
+                out[k] = {"error": r["error"]}
+                continue
+            if r["final_metrics"] is not None:
+                write_reports_packed(names[k], output_directory, r, hints[k])
+            out[k] = r
+    return out
+
+
 def patch_reference(module) -> None:
     """Rebind an imported reference ``bpm_analysis`` module's hot path to the GPU.
 

@@ -123,6 +123,7 @@ class Packed:
     y_max: "object"
     n_raw_troughs: "object" = None
     flags: "object" = None
+    tr_floor: "object" = None      # the floor at the troughs (pack(want_tr_floor=True)), like tr_env
 
     @property
     def n_files(self) -> int:
@@ -135,7 +136,7 @@ class Packed:
 
     def to_host(self) -> List[dict]:
         """Per-file dicts: sr, n_env, peaks, env_pk, floor_pk, troughs, env_tr,
-        n_raw_troughs, flags (and y16, y_max when packed).  Two rounds of
+        n_raw_troughs, flags (and y16, y_max, floor_tr when packed).  Two rounds of
         asynchronous copies into pinned staging on the current stream, each
         ended by one stream synchronise: the per-file offsets and counters
         first, then the used prefix of each table (and y16), whose length
@@ -159,6 +160,8 @@ class Packed:
                    "tr_idx": (self.tr_idx, tt), "tr_env": (self.tr_env, tt)}
             if self.y16 is not None:
                 big["y16"] = (self.y16, tot)
+            if self.tr_floor is not None:
+                big["tr_floor"] = (self.tr_floor, tt)
             pin = {k: det.staging(k, n, t.dtype) for k, (t, n) in big.items() if n > 0}
             for k, h in pin.items():
                 h.copy_(big[k][0][:big[k][1]], non_blocking=True)
@@ -179,12 +182,33 @@ class Packed:
                      n_raw_troughs=int(nraw[f]), flags=int(flags[f]))
             if self.y16 is not None:
                 r["y16"], r["y_max"] = tab["y16"][a:b], float(meta["y_max"][f])
+            if self.tr_floor is not None:
+                r["floor_tr"] = tab["tr_floor"][t0:t1]
             out.append(r)
         return out
 
 
 _NP_OF = {"torch.int8": np.int8, "torch.int16": np.int16, "torch.int32": np.int32, "torch.int64": np.int64,
           "torch.float64": np.float64}
+
+
+@dataclass
+class Trace:
+    """bpmx_trace_out for one batch (device tensors): the decision trace of
+    ``beats_device(trace=True)``, in slices at ``packed.pk_off[f]`` (record:
+    N.TR_NFIELDS doubles per raw peak).  ``explain.assemble`` turns a
+    recording's slices into the reference's ``analysis_data``."""
+    record: "object"
+    code: "object"
+    lt_pos: "object"
+    lt_bpm: "object"
+    n_lt: "object"
+    dev_t: "object"
+    dev: "object"
+    gap: "object"
+
+
+_TRACE_ROWS = ("record", "code", "lt_pos", "lt_bpm", "dev_t", "dev", "gap")
 
 
 @dataclass
@@ -203,8 +227,11 @@ class Beats:
     pass_: "object"
     tags: "object"
     status: "object"
+    trace: Optional[Trace] = None  # beats_device(trace=True)
+    params: Optional[dict] = None  # the parameter dict of the launch (the trace's strings quote thresholds)
+    hints: "object" = None         # device [F] per-file hints the launch reads (kept alive with its results)
 
-    def to_host(self) -> List[dict]:
+    def to_host(self, explain: bool = False) -> List[dict]:
         """Per-file dicts as ``_host.beats`` returns them (final_peaks,
         bpm_times, bpm, start_bpm, peak_time, recovery_time, tags, or
         ``error=KeyError(...)`` for < 2 raw peaks) plus ``raw_peaks`` and
@@ -212,15 +239,25 @@ class Beats:
         ``skipped=True`` with its flags.  Two rounds of copies like
         ``Packed.to_host``: offsets, counts, status and pass values first, then
         the used prefix of each array.  Raises BpmxError (E_LIMIT) when the
-        peak table was too small."""
+        peak table was too small.
+
+        ``explain`` (needs ``beats_device(trace=True)`` with the parameter
+        dict): the trace comes down in the same two rounds and every
+        recording with beats gets ``analysis_data`` (``explain.assemble``: the
+        reference's debug strings, belief curve and deviation series) and
+        ``trace`` (its slices of the trace, as ``explain.assemble`` takes them)."""
         from . import _host
         torch = _torch()
         det, pk = self.det, self.packed
         F = pk.n_files
+        if explain and (self.trace is None or self.params is None):
+            raise N.BpmxError("explain needs beats_device(trace=True) with the parameter dict", N.E_ARG)
         with det.lock:
             st = torch.cuda.current_stream(det.device)
             small = {"pk_off": pk.pk_off, "flags": pk.flags, "b_n_final": self.n_final, "b_n_bpm": self.n_bpm,
                      "b_status": self.status, "b_pass": self.pass_}
+            if explain:
+                small["t_n_lt"] = self.trace.n_lt
             pin = {k: det.staging(k, t.numel(), t.dtype) for k, t in small.items() if t is not None}
             for k, h in pin.items():
                 h.copy_(small[k].reshape(-1), non_blocking=True)
@@ -232,9 +269,13 @@ class Beats:
                 raise N.BpmxError(f"packed tables too small: {tp} peaks (capacity {pk.cap_peaks})", N.E_LIMIT)
             big = {"pk_idx": pk.pk_idx, "b_final": self.final_idx, "b_bpm_t": self.bpm_t, "b_bpm": self.bpm,
                    "b_tags": self.tags}
-            pin = {k: det.staging(k, tp, t.dtype) for k, t in big.items() if tp > 0}
+            per = {k: 1 for k in big}
+            if explain:
+                big.update({"t_" + k: getattr(self.trace, k) for k in _TRACE_ROWS})
+                per.update({"t_" + k: (N.TR_NFIELDS if k == "record" else 1) for k in _TRACE_ROWS})
+            pin = {k: det.staging(k, tp * per[k], t.dtype) for k, t in big.items() if tp > 0}
             for k, h in pin.items():
-                h.copy_(big[k][:tp], non_blocking=True)
+                h.copy_(big[k][:tp * per[k]], non_blocking=True)
             st.synchronize()
             tab = {k: (pin[k].numpy().copy() if k in pin else np.zeros(0, _NP_OF[str(t.dtype)]))
                    for k, t in big.items()}
@@ -258,6 +299,15 @@ class Beats:
                 r.update(final_peaks=fin[a:a + nf], bpm_times=tab["b_bpm_t"][a:a + nb], bpm=tab["b_bpm"][a:a + nb],
                          start_bpm=float(pas[f, 0]), peak_time=nan2none(pas[f, 1]),
                          recovery_time=nan2none(pas[f, 2]), tags=tab["b_tags"][a:a + n])
+                if explain:
+                    from . import explain as X
+                    nl = int(meta["t_n_lt"][f])
+                    tr = dict(record=tab["t_record"][a * N.TR_NFIELDS:(a + n) * N.TR_NFIELDS], code=tab["t_code"][a:a + n],
+                              gap=tab["t_gap"][a:a + n], lt_pos=tab["t_lt_pos"][a:a + nl],
+                              lt_bpm=tab["t_lt_bpm"][a:a + nl], dev_t=tab["t_dev_t"][a:a + n - 1],
+                              dev=tab["t_dev"][a:a + n - 1])
+                    r["trace"] = tr
+                    r["analysis_data"] = X.assemble(r["raw_peaks"], int(pk.sr), self.params, tr)
             out.append(r)
         return out
 
@@ -324,8 +374,8 @@ class Metrics:
         meta["m_record"] = meta["m_record"].reshape(F, N.METRICS_RECORD)
         return meta, tab
 
-    def to_host(self, assemble: bool = True) -> List[dict]:
-        """``Beats.to_host()``'s per-file dicts plus ``final_metrics`` (the dict
+    def to_host(self, assemble: bool = True, explain: bool = False) -> List[dict]:
+        """``Beats.to_host(explain)``'s per-file dicts plus ``final_metrics`` (the dict
         ``beats.final_metrics`` returns, assembled from the device's positions
         and values; None where the reference makes none: fewer than two final
         beats, an error, a skipped recording) and ``metrics_source``.  A
@@ -338,7 +388,7 @@ class Metrics:
         bpmx_metrics_out) and ``n_hrv``, which is all ``run_sharded`` gathers."""
         from . import beats as B
         from . import metrics as MH
-        out = self.beats.to_host()
+        out = self.beats.to_host(explain=explain)
         meta, tab = self.download(rows=assemble)
         pko, sr = meta["pk_off"], int(self.beats.packed.sr)
         for f, r in enumerate(out):
@@ -712,7 +762,8 @@ class Detector:
                       y16=e(tot, torch.int16) if want_y16 else None,
                       y_max=e(F, torch.float64) if want_y16 else None)
 
-    def pack(self, res: Result, distance: int, want_y16: bool = False, out: Optional[Packed] = None) -> Packed:
+    def pack(self, res: Result, distance: int, want_y16: bool = False, out: Optional[Packed] = None,
+             want_tr_floor: bool = False) -> Packed:
         """bpmx_pack on the current stream, behind the run (and any
         ``resolve_ties``) that filled `res`: the per-peak / per-trough tables
         and, with `want_y16` (``res.y`` required), the int16 debug samples.
@@ -720,7 +771,9 @@ class Detector:
         (an `out` from ``alloc_packed`` with its own capacities) are checked
         here, which waits for the stream: BpmxError (E_LIMIT) when a total
         exceeds its capacity; the offsets then still hold the true totals and
-        nothing at or beyond the capacity was written."""
+        nothing at or beyond the capacity was written.  `want_tr_floor`:
+        ``out.tr_floor`` gets the floor at the troughs (bpmx_pack_trough_floor,
+        behind the pack on the same stream), which the debug log reads."""
         if res.peaks is None or res.troughs is None or res.floor is None:
             raise N.BpmxError("pack needs a Result with floor, troughs and peaks", N.E_ARG)
         if out is None:
@@ -745,6 +798,16 @@ class Detector:
         with self.lock:
             N.check(self.L.bpmx_pack(self.ctx, res.n_files, fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                      res.ds, ctypes.byref(o), ctypes.byref(k), self.stream_handle()), "bpmx_pack")
+            if want_tr_floor:
+                if not hasattr(self.L, "bpmx_pack_trough_floor"):
+                    raise N.BpmxError("libbpmx.so has no bpmx_pack_trough_floor; rebuild")
+                if out.tr_floor is None:
+                    torch = _torch()
+                    out.tr_floor = torch.empty(max(int(out.cap_troughs), 1), dtype=torch.float64, device=self.device)
+                N.check(self.L.bpmx_pack_trough_floor(self.ctx, ctypes.byref(o),
+                                                      fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), res.n_files,
+                                                      res.ds, ctypes.byref(k), out.tr_floor.data_ptr(),
+                                                      self.stream_handle()), "bpmx_pack_trough_floor")
         if out.cap_peaks < out.safe_peaks or out.cap_troughs < out.safe_troughs:
             F = res.n_files
             out._check(int(out.pk_off[F].item()), int(out.tr_off[F].item()))
@@ -806,12 +869,18 @@ class Detector:
 
         return self._in_callers_order(go, list(recordings), longest_first)
 
-    def beats_device(self, packed: Packed, params, hint: Optional[float] = None) -> Beats:
+    def beats_device(self, packed: Packed, params, hint: Optional[float] = None,
+                     hints: Optional[Sequence[Optional[float]]] = None, trace: bool = False) -> Beats:
         """bpmx_beats_device on the current stream, behind the ``pack`` that
         filled `packed`: the beat stages (preliminary pass, classifier,
         refinement, BPM curve) of every recording from its peak table, on the
         GPU.  ``params``: the parameter dict or a prepared _host.BeatParams.
-        Asynchronous; outputs are sized by ``packed.cap_peaks``."""
+        Asynchronous; outputs are sized by ``packed.cap_peaks``.
+
+        ``hints``: one start BPM per recording (None = no hint) in place of
+        `hint` for all of them, in the same launch.  ``trace``: the decision
+        trace (``Beats.trace``; bpmx_beats_device_ex, kernel k_beats_trace)
+        beside the same results, for ``Beats.to_host(explain=True)``."""
         from . import _host
         torch = _torch()
         bp = params if isinstance(params, _host.BeatParams) else _host.beat_params(params)
@@ -829,10 +898,36 @@ class Detector:
         o.bpm_t, o.bpm, o.n_bpm = out.bpm_t.data_ptr(), out.bpm.data_ptr(), out.n_bpm.data_ptr()
         o.pass_, o.tags, o.status = out.pass_.data_ptr(), out.tags.data_ptr(), out.status.data_ptr()
         flags = None if packed.flags is None else packed.flags.data_ptr()
+        h0 = float("nan") if hint is None else float(hint)
+        if hints is None and not trace:
+            with self.lock:
+                N.check(self.L.bpmx_beats_device(self.ctx, F, int(packed.sr), ctypes.byref(bp), h0, ctypes.byref(k),
+                                                 flags, ctypes.byref(o), self.stream_handle()), "bpmx_beats_device")
+            return out
+        if not hasattr(self.L, "bpmx_beats_device_ex"):
+            raise N.BpmxError("libbpmx.so has no bpmx_beats_device_ex; rebuild")
+        if not isinstance(params, _host.BeatParams):
+            out.params = dict(params)
+        d_hints = None
+        if hints is not None:
+            if len(hints) != F:
+                raise N.BpmxError("beats_device: hints needs one entry per recording", N.E_ARG)
+            hh = np.array([np.nan if h is None else float(h) for h in hints], dtype=np.float64)
+            d_hints = torch.from_numpy(hh).to(dev)
+        t = None
+        if trace:
+            out.trace = Trace(record=e(cap * N.TR_NFIELDS, torch.float64), code=e(cap, torch.int32),
+                              lt_pos=e(cap, torch.int32), lt_bpm=e(cap, torch.float64), n_lt=e(F, torch.int32),
+                              dev_t=e(cap, torch.float64), dev=e(cap, torch.float64), gap=e(cap, torch.int32))
+            t = N.TraceOut()
+            for name, _ in N.TraceOut._fields_:
+                setattr(t, name, getattr(out.trace, name).data_ptr())
         with self.lock:
-            N.check(self.L.bpmx_beats_device(self.ctx, F, int(packed.sr), ctypes.byref(bp),
-                                             float("nan") if hint is None else float(hint), ctypes.byref(k), flags,
-                                             ctypes.byref(o), self.stream_handle()), "bpmx_beats_device")
+            N.check(self.L.bpmx_beats_device_ex(self.ctx, F, int(packed.sr), ctypes.byref(bp), h0, ctypes.byref(k),
+                                                flags, ctypes.byref(o), None if d_hints is None else d_hints.data_ptr(),
+                                                None if t is None else ctypes.byref(t), self.stream_handle()),
+                    "bpmx_beats_device_ex")
+        out.hints = d_hints              # read by the launch: alive as long as its results
         return out
 
     def set_options(self, options: int) -> None:
@@ -913,6 +1008,45 @@ class Detector:
             return out
 
         return self._in_callers_order(go, list(recordings), longest_first)
+
+    def run_host_reports(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
+                         hints: Optional[Sequence[Optional[float]]] = None, resolve_ties: bool = True,
+                         longest_first: bool = True) -> List[dict]:
+        """Everything the reference's report set needs, with no classifier on
+        the host: upload, run, ``resolve_ties``, ``pack`` (with the floor at
+        the troughs, and the int16 debug samples when
+        ``params['save_filtered_wav']``), ``beats_device`` with per-file
+        `hints` and the decision trace, ``metrics_device``.  Per file the dict
+        of ``Metrics.to_host(explain=True)`` (final_peaks, curve,
+        ``final_metrics``, ``analysis_data``, ...) merged with
+        ``Packed.to_host``'s (sr, n_env, peaks, env_pk, floor_pk, troughs,
+        env_tr, floor_tr, y16, y_max), which is what
+        ``reports.write_reports_packed`` takes.  Same lock, stream and
+        longest-first rules as ``run_host_packed``."""
+        torch = _torch()
+        recordings = list(recordings)
+        if not recordings:
+            return []
+        hints = [None] * len(recordings) if hints is None else list(hints)
+        if len(hints) != len(recordings):
+            raise ValueError("run_host_reports: hints needs one entry per recording")
+        perm = list(range(len(recordings)))
+        if longest_first and len({r.shape[0] for r in recordings}) > 1:
+            from .shard import longest_first as _lf
+            perm = list(_lf([r.shape[0] for r in recordings]))
+        recs, hh = [recordings[i] for i in perm], [hints[i] for i in perm]
+        y16 = bool(params.get("save_filtered_wav", False))
+        with self.lock, torch.cuda.stream(self.host_stream()):
+            res, d = self._batch_on_device(recs, fs, params, mode, N.STAGE_ALL, y16, resolve_ties)
+            pk = self.pack(res, d.distance, want_y16=y16, want_tr_floor=True)
+            b = self.beats_device(pk, params, hints=hh, trace=True)
+            got = self.metrics_device(b, params).to_host(explain=True)
+            tabs = pk.to_host()
+            self.host_stream().synchronize()
+        out: List[dict] = [None] * len(recordings)
+        for k, i in enumerate(perm):
+            out[i] = dict(tabs[k], **got[k])
+        return out
 
     def run_host_y16(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                      stages: int = N.STAGE_ALL, resolve_ties: bool = False, longest_first: bool = True) -> List[dict]:

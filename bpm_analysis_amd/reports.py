@@ -233,3 +233,31 @@ def write_reports(file_name: str, output_directory: str, env, sr, raw_peaks, dat
     with open(os.path.join(output_directory, f"{b}_Debug_Log.md"), "w", encoding="utf-8") as f:
         f.write(debug_log_text(file_name, env, sr, raw_peaks, data, m, now))
     write_settings(file_name, output_directory, start_bpm_hint)
+
+
+def write_reports_packed(file_name: str, output_directory: str, r: Dict, start_bpm_hint: Optional[float],
+                         now=None) -> None:
+    """``write_reports`` and ``<base>_bpm_plot.csv`` for a recording that exists
+    as packed tables only (engine.Detector.run_host_reports): ``r`` holds
+    ``sr``, ``n_env``, ``peaks`` / ``env_pk`` / ``floor_pk``, ``troughs`` /
+    ``env_tr`` / ``floor_tr``, ``analysis_data`` (explain.assemble) and
+    ``final_metrics`` (metrics.assemble or beats.final_metrics).
+
+    The debug log reads env and floor only at the raw peaks and the troughs:
+    every event lies on its own grid index, so the nearest-match join is exact
+    and the forward fill never reaches an event row.  The arrays handed to the
+    unchanged ``summary_text`` / ``debug_log_text`` are therefore NaN except
+    at the events."""
+    from .beats import write_bpm_csv
+    n_env, sr = int(r["n_env"]), r["sr"]
+    pk, tr = np.asarray(r["peaks"], dtype=np.int64), np.asarray(r["troughs"], dtype=np.int64)
+    env, floor = np.full(n_env, np.nan), np.full(n_env, np.nan)
+    env[tr], floor[tr] = r["env_tr"], r["floor_tr"]
+    env[pk], floor[pk] = r["env_pk"], r["floor_pk"]
+    data = dict(r["analysis_data"])
+    data["trough_indices"] = tr
+    data["dynamic_noise_floor_series"] = pd.Series(floor)
+    m = r["final_metrics"]
+    b = _base(file_name)
+    write_bpm_csv(os.path.join(output_directory, f"{b}_bpm_plot.csv"), m)
+    write_reports(file_name, output_directory, env, sr, pk, data, m, start_bpm_hint, now)

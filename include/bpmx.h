@@ -17,6 +17,10 @@
  *   bpmx_beats_device          <- bpm_analysis.py:1734-1757  analyze_wav_file stages 2-5 on
  *                                 those tables (_run_preliminary_pass, PeakClassifier,
  *                                 _refine_and_correct_peaks, calculate_bpm_series)
+ *   bpmx_beats_device_ex       the same with one start hint per file and the decision trace: the
+ *                                 numbers behind analysis_data's debug strings, belief curve and
+ *                                 deviation series (:64-330), for the reference's Debug_Log.md
+ *   bpmx_pack_trough_floor     the floor at the packed troughs (the debug log prints it)
  *   bpmx_metrics_device        <- bpm_analysis.py:1701-1722  _calculate_final_metrics on the beats and
  *                                 the curve (HRV table, summary, HRR, slopes, inclines and declines)
  *   bpmx_synth / bpmx_synth_host   deterministic synthetic recordings (bench/tests)
@@ -328,6 +332,79 @@ typedef struct {            /* device; per-file slices start at pk_off[f], like 
 int bpmx_beats_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
                       double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
                       const bpmx_beats_out *out, void *stream);
+
+/* The decision trace of the beat stages (bpmx_beats_device_ex).
+ *
+ * What the reference keeps per file to explain its decisions (analysis_data:
+ * beat_debug_info, long_term_bpm_series, deviation_series), as numbers: the
+ * main classification pass stores every value its debug strings format, and
+ * the gap fill which label each of its passes gave a peak.  The host turns
+ * them into the reference's strings (bpm_analysis_amd/explain.py); values are
+ * f64 because the strings round them and only identical doubles give
+ * identical text.  Thresholds and weights are parameters the host has.
+ *
+ * record: BPMX_TR_NFIELDS doubles per raw peak.  A field is written only when
+ * the peak's code announces it (everything else is left as it was):
+ *   every peak but the last and an S2: BLEND, BASE_CONF, FINAL
+ *   BPMX_TRF_STABILITY: STAB_FACTOR, STAB_RATIO    (>= 5 beats so far)
+ *   BPMX_TRF_PENALIZED: ADJ_AMOUNT, ADJ_RATIO (S2/S1), ADJ_RMAX
+ *   BPMX_TRF_BOOSTED:   ADJ_AMOUNT, ADJ_RATIO (S1/S2)
+ *   BPMX_TRF_INTERVAL:  IV_AMOUNT, IV_GAP, IV_CAP
+ *   LONE_VALID, CASCADE, NOISE: the six L_* fields of the Lone-S1 test, and
+ *   L_IMPLIED with BPMX_TRF_FORWARD (the failed forward check)
+ * An S2 (BPMX_TR_S2_PAIRED) has no record: its string is that of the S1 one
+ * table position before it. */
+enum bpmx_trace_field {
+    BPMX_TR_BLEND = 0,          /* share of the high-BPM confidence curve */
+    BPMX_TR_BASE_CONF = 1,      /* blended pairing confidence, may be NaN */
+    BPMX_TR_STAB_FACTOR = 2, BPMX_TR_STAB_RATIO = 3,
+    BPMX_TR_ADJ_AMOUNT = 4, BPMX_TR_ADJ_RATIO = 5, BPMX_TR_ADJ_RMAX = 6,
+    BPMX_TR_IV_AMOUNT = 7, BPMX_TR_IV_GAP = 8, BPMX_TR_IV_CAP = 9,
+    BPMX_TR_FINAL = 10,         /* the score compared with the pairing threshold */
+    BPMX_TR_L_RHYTHM = 11, BPMX_TR_L_RR = 12, BPMX_TR_L_EXPECTED = 13, BPMX_TR_L_AMP = 14, BPMX_TR_L_RATIO = 15,
+    BPMX_TR_L_CONF = 16,
+    BPMX_TR_L_IMPLIED = 17,     /* BPM the next raw peak would imply */
+    BPMX_TR_NFIELDS = 18
+};
+enum bpmx_trace_code {          /* code = outcome | optional lines */
+    BPMX_TR_S1_PAIRED = 1, BPMX_TR_S2_PAIRED = 2, BPMX_TR_LONE_VALID = 3, BPMX_TR_FIRST_BEAT = 4,
+    BPMX_TR_LAST_PEAK = 5, BPMX_TR_CASCADE = 6, BPMX_TR_NOISE = 7,
+    BPMX_TR_OUTCOME = 15,       /* mask */
+    BPMX_TRF_STABILITY = 16, BPMX_TRF_PENALIZED = 32, BPMX_TRF_BOOSTED = 64, BPMX_TRF_INTERVAL = 128,
+    BPMX_TRF_FORWARD = 256      /* NOISE: rejected by the forward check, not by confidence */
+};
+enum bpmx_trace_gap {           /* gap[j] >> (2 * pass) & 3, pass 0..4 of the gap fill */
+    BPMX_TR_GAP_NONE = 0, BPMX_TR_GAP_S1 = 1, BPMX_TR_GAP_S2 = 2
+};
+
+typedef struct {            /* device; per-file slices start at pk_off[f], like the peak table */
+    double  *record;        /* [cap_peaks][BPMX_TR_NFIELDS] */
+    int32_t *code;          /* [cap_peaks] bpmx_trace_code per raw peak */
+    int32_t *lt_pos;        /* [cap_peaks] table position of the last beat after each classifier iteration */
+    double  *lt_bpm;        /* [cap_peaks] the long-term BPM after it; n_lt[f] valid */
+    int32_t *n_lt;          /* [n_files] */
+    double  *dev_t, *dev;   /* [cap_peaks] smoothed deviation series of the main pass, n - 1 valid */
+    int32_t *gap;           /* [cap_peaks] bpmx_trace_gap of each gap-fill pass */
+} bpmx_trace_out;
+
+/* bpmx_beats_device with per-file hints and the decision trace, both optional
+ * (both NULL: bpmx_beats_device).  hints: device [n_files], NaN = None; file
+ * f starts from hints[f] when that is neither NaN nor 0, as start_bpm_hint
+ * does for all files.  trace: every pointer required.  A recording of >= 2
+ * raw peaks writes a code and a gap entry per raw peak, n - 1 deviations and
+ * n_lt[f] beliefs; one of fewer writes n_lt[f] = 0 only; one that reports
+ * BPMX_BEATS_SKIPPED or BPMX_BEATS_OVERFLOW writes nothing of the trace. */
+int bpmx_beats_device_ex(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_beat_params *params,
+                         double start_bpm_hint, const bpmx_packed *in, const int32_t *flags,
+                         const bpmx_beats_out *out, const double *hints, const bpmx_trace_out *trace,
+                         void *stream);
+
+/* tr_floor[j] = floor[D_f + tr_idx[j]] for the trough table of a bpmx_pack
+ * (tr_off, tr_idx; `in` as given to that pack: in->floor is read), copied bit
+ * for bit; an entry at or beyond cap_troughs is not written.  Asynchronous on
+ * `stream`, ordered after the pack.  frame_offsets / ds as for bpmx_pack. */
+int bpmx_pack_trough_floor(bpmx_ctx *ctx, const bpmx_out *in, const int64_t *frame_offsets, int32_t n_files,
+                           int32_t ds, const bpmx_packed *tables, double *tr_floor, void *stream);
 
 /* The final metrics on the device (bpmx_metrics_device).
  *
