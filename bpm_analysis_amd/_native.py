@@ -57,7 +57,7 @@ TR_GAP_NONE, TR_GAP_S1, TR_GAP_S2 = 0, 1, 2
 EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy", "bpmx_decimated_length",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
            "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
-           "bpmx_beats_device_ex", "bpmx_pack_trough_floor"]
+           "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot"]
 
 
 class Params(ctypes.Structure):
@@ -221,6 +221,12 @@ def load() -> ctypes.CDLL:
         L.bpmx_pack_trough_floor.argtypes = [P, ctypes.POINTER(Out), ctypes.POINTER(ctypes.c_int64), I32, I32,
                                              ctypes.POINTER(PackedOut), P, P]
         L.bpmx_pack_trough_floor.restype = ctypes.c_int
+    if hasattr(L, "bpmx_pack_plot"):
+        L.bpmx_plot_length.argtypes = [I64, I32]
+        L.bpmx_plot_length.restype = I64
+        L.bpmx_pack_plot.argtypes = [P, I32, ctypes.POINTER(ctypes.c_int64), I32, I32, ctypes.POINTER(Out), P, P,
+                                     I64, P]
+        L.bpmx_pack_plot.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

@@ -715,9 +715,10 @@ def analyze_fast(results: Sequence[Dict], params: Dict, start_bpm_hint: Optional
     tags), or the entry's / the stage's ``error``.  The same beats and curve
     as ``analyze_recording`` (tests/test_host_beats.py); HRV, slopes, reports
     and the plot stay with analyze_recording on this route.  (The device route
-    has them but the plot: ``Detector.run_host_reports`` /
+    has them all: ``Detector.run_host_reports`` /
     ``dropin.analyze_wav_files_to_reports`` with the decision trace,
-    ``explain.py`` and ``reports.write_reports_packed``.)
+    ``explain.py``, ``reports.write_reports_packed`` and, with ``plot=True``,
+    ``plot.write_plot_packed``.)
 
     Packed per-file dicts (engine.Packed.to_host: ``env_pk`` / ``floor_pk`` at
     the raw peaks instead of whole arrays) run through ``_host.beats_packed``

@@ -1,8 +1,8 @@
 /*
  * bpmx_api.hip — host side of the C ABI (include/bpmx.h): context, scratch,
  * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
- * bpmx_pack_trough_floor, bpmx_beats_device, bpmx_beats_device_ex and
- * bpmx_metrics_device.
+ * bpmx_pack_trough_floor, bpmx_pack_plot, bpmx_beats_device,
+ * bpmx_beats_device_ex and bpmx_metrics_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -151,6 +151,12 @@ void bpmx_destroy(bpmx_ctx *ctx) {
 int64_t bpmx_decimated_length(int64_t n_frames, int32_t ds) {
     if (ds < 1) ds = 1;
     return n_frames <= 0 ? 0 : (n_frames + ds - 1) / ds;
+}
+
+int64_t bpmx_plot_length(int64_t nd, int32_t factor) {
+    if (nd <= 0) return 0;
+    const int64_t kf = (factor > 1 && nd >= factor) ? factor : 1;
+    return (nd + kf - 1) / kf;
 }
 
 void bpmx_synth_host(uint64_t seed, int64_t n_frames, int32_t fs, int32_t channels, int16_t *out) {
@@ -591,6 +597,56 @@ int bpmx_pack_trough_floor(bpmx_ctx *ctx, const bpmx_out *in, const int64_t *fra
     a.doff = d_doff; a.tr_off = tables->tr_off; a.tr_idx = tables->tr_idx; a.floor = in->floor;
     a.cap = tables->cap_troughs; a.out = tr_floor;
     LAUNCH(ctx, s, "k_pack_trough_floor", k_pack_trough_floor, dim3(n_files), dim3(PK_GATHER_T), 0, s, a);
+    return BPMX_OK;
+}
+
+int bpmx_pack_plot(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t factor,
+                   const bpmx_out *in, double *pl_env, double *pl_floor, int64_t cap, void *stream) {
+    if (!ctx || !frame_offsets || !in || !pl_env) return fail(BPMX_E_ARG, "bpmx_pack_plot: NULL argument");
+    const int64_t F = n_files;
+    if (F < 1 || ds < 1 || cap < 0) return fail(BPMX_E_ARG, "bpmx_pack_plot: bad n_files/ds/cap");
+    if (!in->env || (pl_floor && !in->floor)) return fail(BPMX_E_ARG, "bpmx_pack_plot: needs env, and floor for pl_floor");
+    /* doff | poff | boff | kf | file of each workgroup (PlotArgs) */
+    std::vector<int64_t> geo((size_t)(4 * F + 3));
+    int64_t *doff = geo.data(), *poff = doff + F + 1, *boff = poff + F + 1, *kfs = boff + F + 1;
+    doff[0] = poff[0] = boff[0] = 0;
+    for (int64_t f = 0; f < F; ++f) {
+        const int64_t n = frame_offsets[f + 1] - frame_offsets[f];
+        if (n < 0) return fail(BPMX_E_ARG, "frame offsets must be non-decreasing");
+        const int64_t nd = bpmx_decimated_length(n, ds);
+        if (nd >= (int64_t)INT_MAX / 2) return fail(BPMX_E_LIMIT, "recording too long");
+        const int64_t np = bpmx_plot_length(nd, factor);
+        kfs[f] = (factor > 1 && nd >= factor) ? factor : 1;
+        doff[f + 1] = doff[f] + nd;
+        poff[f + 1] = poff[f] + np;
+        boff[f + 1] = boff[f] + (np + PK_PLOT_CHUNK - 1) / PK_PLOT_CHUNK;
+    }
+    const int64_t total = poff[F], nb = boff[F];
+    if (total > cap)
+        return fail(BPMX_E_ARG, "bpmx_pack_plot: " + std::to_string(total) + " kept entries exceed cap " +
+                                    std::to_string(cap));
+    if (nb >= (int64_t)INT_MAX) return fail(BPMX_E_LIMIT, "bpmx_pack_plot: batch too long");
+    if (nb == 0) return BPMX_OK;
+    geo.resize((size_t)(4 * F + 3 + nb));
+    boff = geo.data() + 2 * (F + 1);
+    for (int64_t f = 0; f < F; ++f)
+        for (int64_t b = boff[f]; b < boff[f + 1]; ++b) geo[(size_t)(4 * F + 3 + b)] = f;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = BPMX_OK;
+    bool grew = false;
+    int64_t *d_geo = (int64_t *)ctx->buf("plot_geo", geo.size() * 8, &rc, &grew);
+    if (rc != BPMX_OK) return rc;
+    if (grew || geo != ctx->plot_key) {
+        /* stream-ordered: launches of an earlier call still read the old geometry */
+        ctx->plot_key.swap(geo);
+        HIP_TRY(hipMemcpyAsync(d_geo, ctx->plot_key.data(), ctx->plot_key.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    PlotArgs a{};
+    a.geo = d_geo; a.n_files = n_files;
+    a.src[0] = in->env; a.dst[0] = pl_env;
+    a.src[1] = in->floor; a.dst[1] = pl_floor;
+    LAUNCH(ctx, s, "k_pack_plot", k_pack_plot, dim3((unsigned)nb, pl_floor ? 2 : 1), dim3(PK_PLOT_T), 0, s, a);
     return BPMX_OK;
 }
 

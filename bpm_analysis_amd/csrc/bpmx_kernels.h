@@ -550,6 +550,19 @@ struct TroughFloorArgs {
 };
 __global__ void k_pack_trough_floor(TroughFloorArgs A);
 
+/* bpmx_pack_plot (k_pack.hip): workgroup x copies one chunk of PK_PLOT_CHUNK
+ * kept entries of one file, y = 0 the envelope, 1 the floor.  geo is one
+ * upload: doff[F+1] | poff[F+1] | first workgroup of each file [F+1] |
+ * kf[F] | the file of each workgroup [boff[F]] */
+enum { PK_PLOT_T = 256, PK_PLOT_CHUNK = 2048 };
+struct PlotArgs {
+    const int64_t *geo;
+    int32_t n_files;
+    const double *src[2];
+    double *dst[2];
+};
+__global__ void k_pack_plot(PlotArgs A);
+
 /* bpmx_metrics_device (k_metrics.hip): one workgroup of METRICS_T threads per recording */
 enum { METRICS_T = 256 };
 struct MetricsArgs {

@@ -10,6 +10,10 @@
  *                   table position is at or beyond the capacity are dropped
  *   k_pack_trough_floor  bpmx_pack_trough_floor: the floor at the packed
  *                   troughs, from the table's own offsets and indices
+ *   k_pack_plot     bpmx_pack_plot: env and floor at every kf-th sample of each
+ *                   file, per workgroup one chunk of kept entries; at kf = 1
+ *                   16 bytes per lane where source and destination share
+ *                   their 16-byte phase
  *   k_y16_max       per file max|y|: |y| bit patterns order as unsigned
  *                   integers and every NaN pattern lies above inf, so a 64-bit
  *                   atomic maximum of the bits propagates a NaN by itself
@@ -99,6 +103,39 @@ __global__ __launch_bounds__(PK_GATHER_T) void k_pack_trough_floor(TroughFloorAr
     for (int64_t j = o + threadIdx.x; j < e; j += PK_GATHER_T) {
         const int64_t i = A.tr_idx[j];
         out[j] = (i >= 0 && i < nd) ? flo[i] : QNAN_BITS;
+    }
+}
+
+/* dst[P_f + j] = src[D_f + j * kf] as bit patterns, j in this workgroup's chunk
+ * of file f's kept entries (the host lists a workgroup per non-empty chunk, so
+ * 1 <= m <= PK_PLOT_CHUNK).  Writes are contiguous 8 or 16 bytes per lane.  At
+ * kf > 1 the reads are one 8-byte word per lane kf words apart: no word is
+ * read twice, and up to kf = 8 a wave still uses every 64-byte line it
+ * touches, beyond that a line per lane, which is what a strided gather costs
+ * anywhere; the source is read once, so nothing is staged in LDS. */
+__global__ __launch_bounds__(PK_PLOT_T) void k_pack_plot(PlotArgs A) {
+    const int64_t F = A.n_files;
+    const int64_t *doff = A.geo, *poff = doff + F + 1, *boff = poff + F + 1, *kfs = boff + F + 1, *bfile = kfs + F;
+    const int64_t f = bfile[blockIdx.x];
+    const int64_t kf = kfs[f];
+    const int64_t j0 = ((int64_t)blockIdx.x - boff[f]) * PK_PLOT_CHUNK;
+    int64_t m = poff[f + 1] - poff[f] - j0;
+    if (m > PK_PLOT_CHUNK) m = PK_PLOT_CHUNK;
+    if (m <= 0) return;
+    const u64 *src = (const u64 *)A.src[blockIdx.y] + doff[f] + j0 * kf;
+    u64 *dst = (u64 *)A.dst[blockIdx.y] + poff[f] + j0;
+    const int t = threadIdx.x;
+    if (kf == 1 && !(((uintptr_t)src ^ (uintptr_t)dst) & 8)) {
+        /* a scalar head up to the first 16-byte boundary, pairs, a scalar tail */
+        const int64_t lo = ((uintptr_t)dst & 8) ? 1 : 0;
+        const int64_t npair = (m - lo) / 2;
+        if (t == 0 && lo) dst[0] = src[0];
+        if (t == 1 && lo + 2 * npair < m) dst[m - 1] = src[m - 1];
+        const ulonglong2 *s2 = (const ulonglong2 *)(src + lo);
+        ulonglong2 *d2 = (ulonglong2 *)(dst + lo);
+        for (int64_t q = t; q < npair; q += PK_PLOT_T) d2[q] = s2[q];
+    } else {
+        for (int64_t j = t; j < m; j += PK_PLOT_T) dst[j] = src[j * kf];
     }
 }
 

@@ -297,13 +297,18 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
 
 def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output_directory: str,
                                  start_bpm_hints: Sequence = None, original_file_paths: Sequence[str] = None,
-                                 mode: str = None, device: int = 0) -> List[dict]:
+                                 mode: str = None, device: int = 0, plot: bool = False) -> List[dict]:
     """``beats.analyze_wav_file`` for many WAV files with every stage on the
     device: per file ``<base>_bpm_plot.csv``, ``<base>_Analysis_Summary.md``,
     ``<base>_Debug_Log.md`` and ``<base>_Analysis_Settings.json`` (and both
     debug WAVs with ``params["save_filtered_wav"]``), byte for byte what
     ``analyze_wav_file`` writes apart from the markdown files' timestamp line.
-    The plot (``<base>_bpm_plot.html``) needs whole envelopes and is not made.
+    With ``plot=True`` the interactive plot ``<base>_bpm_plot.html`` is written
+    too, before the other files as ``analyze_wav_file`` does, and the figure is
+    returned as the dict's ``figure`` (what the Gradio app displays): its two
+    line traces come from ``Detector.pack_plot`` (the envelope and the floor at
+    every ``plot_downsample_factor``-th sample), everything else from the
+    tables, through ``plot.write_plot_packed``.
 
     Files are read and grouped as ``analyze_wav_files`` does; each group is one
     ``Detector.run_host_reports``: hot path, tables, beat stages with one start
@@ -318,6 +323,7 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     ``error`` with the exception the reference raises for that file; as there,
     a file with fewer than two final beats gets no reports
     (``final_metrics`` None)."""
+    from .plot import write_plot_packed
     from .reports import write_reports_packed
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
@@ -351,7 +357,7 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
             if d.distance < 1:
                 raise ValueError(DISTANCE_MSG)
             res = det.run_host_reports([audio[k][1] for k in idx], fs, params, mode=mode,
-                                       hints=[hints[k] for k in idx])
+                                       hints=[hints[k] for k in idx], plot=plot)
         except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
@@ -370,6 +376,8 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                 out[k] = {"error": r["error"]}
                 continue
             if r["final_metrics"] is not None:
+                if plot:
+                    r["figure"] = write_plot_packed(names[k], output_directory, params, r)
                 write_reports_packed(names[k], output_directory, r, hints[k])
             out[k] = r
     return out

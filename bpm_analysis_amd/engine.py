@@ -192,6 +192,61 @@ _NP_OF = {"torch.int8": np.int8, "torch.int16": np.int16, "torch.int32": np.int3
           "torch.float64": np.float64}
 
 
+def plot_device_factor(factor) -> int:
+    """The int32 factor bpmx_pack_plot takes for a ``plot_downsample_factor``
+    as the reference's parameters hold it.  The reference strides by it only
+    when ``factor > 1 and len(env) >= factor`` and fails in the slice when it
+    is then not an integer, so whatever is not an integer above 1 keeps whole
+    series (factor 1) for ``plot.build_figure`` to accept or refuse as it does
+    dense arrays; an integer beyond int32 exceeds every recording."""
+    if isinstance(factor, (int, np.integer)) and factor > 1:
+        return int(min(int(factor), 2 ** 31 - 1))
+    return 1
+
+
+@dataclass
+class PlotSeries:
+    """The plot's two line traces for one batch (device tensors): per
+    recording ``env[::kf]`` and ``floor[::kf]``, ragged, recording f's entries
+    at ``[off[f], off[f + 1])``; `kf` and `off` are host arrays (the lengths
+    follow from the decimated lengths and the factor alone).  When every kf
+    is 1, `env` and `floor` are the Result's own tensors and `off` its
+    decimated offsets: nothing was launched or copied on the device."""
+    det: "object"
+    factor: int
+    kf: np.ndarray                 # host int64 [F]
+    off: np.ndarray                # host int64 [F+1]
+    env: "object"
+    floor: "object"                # None without want_floor
+
+    @property
+    def n_files(self) -> int:
+        return len(self.off) - 1
+
+    def to_host(self) -> List[dict]:
+        """Per-file dicts: ``env_plot``, ``floor_plot`` (None without the
+        floor) and ``plot_factor`` (the kf used).  Asynchronous copies of the
+        used prefixes into pinned staging on the current stream, one wait."""
+        torch = _torch()
+        det, F, tot = self.det, self.n_files, int(self.off[-1])
+        with det.lock:
+            st = torch.cuda.current_stream(det.device)
+            src = {"pl_env": self.env, "pl_floor": self.floor}
+            pin = {k: det.staging(k, tot, t.dtype) for k, t in src.items() if t is not None and tot > 0}
+            for k, h in pin.items():
+                h.copy_(src[k][:tot], non_blocking=True)
+            st.synchronize()
+            tab = {k: h.numpy().copy() for k, h in pin.items()}
+        env = tab.get("pl_env", np.zeros(0))
+        flo = tab.get("pl_floor", np.zeros(0)) if self.floor is not None else None
+        out = []
+        for f in range(F):
+            a, b = int(self.off[f]), int(self.off[f + 1])
+            out.append(dict(env_plot=env[a:b], floor_plot=None if flo is None else flo[a:b],
+                            plot_factor=int(self.kf[f])))
+        return out
+
+
 @dataclass
 class Trace:
     """bpmx_trace_out for one batch (device tensors): the decision trace of
@@ -813,6 +868,50 @@ class Detector:
             out._check(int(out.pk_off[F].item()), int(out.tr_off[F].item()))
         return out
 
+    def pack_plot(self, res: Result, factor: int, want_floor: bool = True, out=None) -> PlotSeries:
+        """The plot's line traces of `res` at ``plot_downsample_factor``
+        `factor` (an integer): per recording ``env[::kf]`` and ``floor[::kf]``
+        with the reference's rule for kf (bpmx_plot_length), made by
+        bpmx_pack_plot on the current stream behind the run.  Asynchronous.
+        When every recording's kf is 1 (the shipped factor) the series are
+        ``res.env`` / ``res.floor`` themselves and nothing is launched.
+        `out`: (env, floor) device float64 tensors to fill instead (floor None
+        without `want_floor`); then the kernel always runs, and a total above
+        their length is a BpmxArgError with nothing written."""
+        if res.env is None or (want_floor and res.floor is None):
+            raise N.BpmxError("pack_plot needs a Result with env (and floor)", N.E_ARG)
+        if not hasattr(self.L, "bpmx_pack_plot"):
+            raise N.BpmxError("libbpmx.so has no bpmx_pack_plot; rebuild")
+        factor = int(factor)
+        if not -2 ** 31 <= factor < 2 ** 31:
+            raise N.BpmxError("pack_plot: factor outside int32 (plot_device_factor clamps it)", N.E_ARG)
+        nd = np.diff(res.doff)
+        n = np.array([self.L.bpmx_plot_length(int(x), factor) for x in nd], dtype=np.int64)
+        kf = np.where(n == nd, 1, factor).astype(np.int64)
+        off = np.zeros(res.n_files + 1, dtype=np.int64)
+        off[1:] = np.cumsum(n)
+        if out is None and bool((kf == 1).all()):
+            return PlotSeries(det=self, factor=factor, kf=kf, off=off, env=res.env,
+                              floor=res.floor if want_floor else None)
+        torch = _torch()
+        if out is None:
+            e = lambda: torch.empty(max(int(off[-1]), 1), dtype=torch.float64, device=self.device)
+            out = (e(), e() if want_floor else None)
+        oe, of = out
+        if of is not None and not want_floor:
+            of = None
+        cap = oe.numel() if of is None else min(oe.numel(), of.numel())
+        o = N.Out()
+        o.env = res.env.data_ptr()
+        o.floor = None if res.floor is None else res.floor.data_ptr()
+        fo = res.frame_offsets
+        with self.lock:
+            N.check(self.L.bpmx_pack_plot(self.ctx, res.n_files, fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                          res.ds, factor, ctypes.byref(o), oe.data_ptr(),
+                                          None if of is None else of.data_ptr(), cap, self.stream_handle()),
+                    "bpmx_pack_plot")
+        return PlotSeries(det=self, factor=factor, kf=kf, off=off, env=oe, floor=of)
+
     def _batch_on_device(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str, stages: int,
                          want_y: bool, resolve_ties: bool, options: int = 0):
         """Upload one batch, run it and re-decide its ties (the caller holds the
@@ -1011,7 +1110,7 @@ class Detector:
 
     def run_host_reports(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                          hints: Optional[Sequence[Optional[float]]] = None, resolve_ties: bool = True,
-                         longest_first: bool = True) -> List[dict]:
+                         longest_first: bool = True, plot: bool = False) -> List[dict]:
         """Everything the reference's report set needs, with no classifier on
         the host: upload, run, ``resolve_ties``, ``pack`` (with the floor at
         the troughs, and the int16 debug samples when
@@ -1021,8 +1120,11 @@ class Detector:
         ``final_metrics``, ``analysis_data``, ...) merged with
         ``Packed.to_host``'s (sr, n_env, peaks, env_pk, floor_pk, troughs,
         env_tr, floor_tr, y16, y_max), which is what
-        ``reports.write_reports_packed`` takes.  Same lock, stream and
-        longest-first rules as ``run_host_packed``."""
+        ``reports.write_reports_packed`` takes.  With `plot`, each dict also
+        carries ``env_plot``, ``floor_plot`` and ``plot_factor``
+        (``pack_plot`` at ``params['plot_downsample_factor']``, default 5 as in
+        the reference), which ``plot.build_figure_packed`` takes.  Same lock,
+        stream and longest-first rules as ``run_host_packed``."""
         torch = _torch()
         recordings = list(recordings)
         if not recordings:
@@ -1039,13 +1141,21 @@ class Detector:
         with self.lock, torch.cuda.stream(self.host_stream()):
             res, d = self._batch_on_device(recs, fs, params, mode, N.STAGE_ALL, y16, resolve_ties)
             pk = self.pack(res, d.distance, want_y16=y16, want_tr_floor=True)
+            if plot:
+                ps = self.pack_plot(res, plot_device_factor(params.get("plot_downsample_factor", 5)))
             b = self.beats_device(pk, params, hints=hh, trace=True)
             got = self.metrics_device(b, params).to_host(explain=True)
             tabs = pk.to_host()
+            if plot:
+                series = ps.to_host()
             self.host_stream().synchronize()
         out: List[dict] = [None] * len(recordings)
         for k, i in enumerate(perm):
             out[i] = dict(tabs[k], **got[k])
+            if plot:
+                if tabs[k]["flags"] & N.F_TOO_SHORT:    # no outputs: empty series, not the buffers' old contents
+                    series[k]["env_plot"], series[k]["floor_plot"] = np.zeros(0), np.zeros(0)
+                out[i].update(series[k])
         return out
 
     def run_host_y16(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",

@@ -7,6 +7,9 @@ and HRV traces, slope segments, min/max and summary annotations, the dark
 layout with mm:ss ticks.  ``write_plot`` saves ``<base>_bpm_plot.html`` and
 returns the figure (what the Gradio app displays).  Parity: the figure's
 plotly JSON equals the reference's (tests/test_beats.py::test_plot_matches_reference).
+``build_figure_packed`` / ``write_plot_packed`` give the same figure for a
+recording the device route holds as packed tables and the two plot series
+(bpmx_pack_plot) instead of whole arrays.
 """
 from __future__ import annotations
 
@@ -202,3 +205,49 @@ def write_plot(file_name: str, output_directory: str, params: Dict, sr: int, env
     fig.write_html(os.path.join(output_directory, f"{base}_bpm_plot.html"),
                    config={'scrollZoom': True, 'toImageButtonOptions': {'filename': title, 'format': 'png', 'scale': 2}})
     return fig
+
+
+def _sparse_inputs(r: Dict):
+    """Dense-shaped (env, raw peaks, analysis_data) of a recording that exists
+    as packed tables and plot series only (engine.Detector.run_host_reports
+    with ``plot=True``).  ``build_figure`` reads env and floor at every k-th
+    sample, at the troughs and at the raw peaks and nowhere else, so arrays
+    that are NaN except there give the same figure; the amplitude axis takes
+    its quantile from the envelope trace, which holds kept samples only.
+    ``plot_factor`` is the stride the series were kept at: the reference's
+    choice for an integer ``plot_downsample_factor``, and 1 (whole series) for
+    anything else, which ``build_figure`` then takes or refuses as it does a
+    dense array."""
+    n_env, kf = int(r["n_env"]), int(r["plot_factor"])
+    pk, tr = np.asarray(r["peaks"], dtype=np.int64), np.asarray(r["troughs"], dtype=np.int64)
+    env, floor = np.full(n_env, np.nan), np.full(n_env, np.nan)
+    env[::kf] = r["env_plot"]
+    have_floor = r.get("floor_plot") is not None
+    if have_floor:
+        floor[::kf] = r["floor_plot"]
+    env[tr] = r["env_tr"]
+    env[pk] = r["env_pk"]
+    data = dict(r["analysis_data"])
+    data["trough_indices"] = tr
+    if have_floor:
+        floor[tr], floor[pk] = r["floor_tr"], r["floor_pk"]
+        data["dynamic_noise_floor_series"] = pd.Series(floor)
+    else:
+        data["dynamic_noise_floor_series"] = None
+    return env, pk, data
+
+
+def build_figure_packed(file_name: str, params: Dict, r: Dict):
+    """``build_figure`` from packed tables: ``r`` holds ``sr``, ``n_env``,
+    ``peaks`` / ``env_pk`` / ``floor_pk``, ``troughs`` / ``env_tr`` /
+    ``floor_tr``, ``env_plot`` / ``floor_plot`` / ``plot_factor``,
+    ``analysis_data`` and ``final_metrics``.  The same plotly JSON as the dense
+    route's (tests/test_plot_packed.py)."""
+    env, pk, data = _sparse_inputs(r)
+    return build_figure(file_name, params, r["sr"], env, pk, data, r["final_metrics"])
+
+
+def write_plot_packed(file_name: str, output_directory: str, params: Dict, r: Dict) -> Optional[object]:
+    """``write_plot`` from packed tables (``build_figure_packed``'s `r`)."""
+    env, pk, data = _sparse_inputs(r)
+    return write_plot(file_name, output_directory, params, r["sr"], env, pk, data, r["final_metrics"])

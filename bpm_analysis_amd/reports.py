@@ -241,7 +241,9 @@ def write_reports_packed(file_name: str, output_directory: str, r: Dict, start_b
     as packed tables only (engine.Detector.run_host_reports): ``r`` holds
     ``sr``, ``n_env``, ``peaks`` / ``env_pk`` / ``floor_pk``, ``troughs`` /
     ``env_tr`` / ``floor_tr``, ``analysis_data`` (explain.assemble) and
-    ``final_metrics`` (metrics.assemble or beats.final_metrics).
+    ``final_metrics`` (metrics.assemble or beats.final_metrics).  The plot
+    from the same dict (with the plot series of ``run_host_reports(plot=True)``)
+    is ``plot.write_plot_packed``.
 
     The debug log reads env and floor only at the raw peaks and the troughs:
     every event lies on its own grid index, so the nearest-match join is exact

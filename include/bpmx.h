@@ -21,6 +21,8 @@
  *                                 numbers behind analysis_data's debug strings, belief curve and
  *                                 deviation series (:64-330), for the reference's Debug_Log.md
  *   bpmx_pack_trough_floor     the floor at the packed troughs (the debug log prints it)
+ *   bpmx_pack_plot             <- bpm_analysis.py:518-524  the plot's line traces: env and floor at every
+ *                                 plot_downsample_factor-th sample
  *   bpmx_metrics_device        <- bpm_analysis.py:1701-1722  _calculate_final_metrics on the beats and
  *                                 the curve (HRV table, summary, HRR, slopes, inclines and declines)
  *   bpmx_synth / bpmx_synth_host   deterministic synthetic recordings (bench/tests)
@@ -405,6 +407,31 @@ int bpmx_beats_device_ex(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_
  * `stream`, ordered after the pack.  frame_offsets / ds as for bpmx_pack. */
 int bpmx_pack_trough_floor(bpmx_ctx *ctx, const bpmx_out *in, const int64_t *frame_offsets, int32_t n_files,
                            int32_t ds, const bpmx_packed *tables, double *tr_floor, void *stream);
+
+/* The analysis plot's two line traces (bpmx_pack_plot).
+ *
+ * The figure reads the envelope and the floor at the raw peaks and the
+ * troughs (bpmx_pack's tables) and, for its two line traces, at every k-th
+ * sample, k = plot_downsample_factor (bpm_analysis.py:518-524).  Per file the
+ * reference's rule: kf = factor when factor > 1 and Nd_f >= factor, else 1;
+ * n_f = bpmx_plot_length(Nd_f, factor) = ceil(Nd_f / kf) entries are kept:
+ *
+ *   P_f = sum_{g<f} n_g
+ *   for j < n_f:  pl_env[P_f + j] = env[D_f + j * kf]   (pl_floor likewise)
+ *
+ * copied as 64-bit patterns.  The offsets follow from frame_offsets, ds and
+ * factor alone, so the host knows them (and the total, P_{n_files}) without
+ * asking the device.  File flags are not consulted. */
+int64_t bpmx_plot_length(int64_t nd, int32_t factor);
+
+/* in->env (required) and in->floor (read when pl_floor is set; pl_floor NULL:
+ * no floor series) -> pl_env, pl_floor: device [cap] entries.  A total above
+ * cap is BPMX_E_ARG, before anything is launched; nothing outside [0, total)
+ * of either output is written.  One launch, asynchronous on `stream` (the
+ * run's, or one ordered after it), no host synchronisation; scratch comes
+ * from ctx.  frame_offsets / ds as for bpmx_pack. */
+int bpmx_pack_plot(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t factor,
+                   const bpmx_out *in, double *pl_env, double *pl_floor, int64_t cap, void *stream);
 
 /* The final metrics on the device (bpmx_metrics_device).
  *
