@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("BPMX_LIB") or os.path.join(_HERE, "libbpmx.so")
 ABI_VERSION = 4
 
 DT_U8, DT_I16, DT_I32, DT_F32, DT_F64 = 0, 1, 2, 3, 4
-MODE_REFERENCE, MODE_NATIVE = 0, 1
+MODE_REFERENCE, MODE_NATIVE, MODE_RECTIFIED = 0, 1, 2
 STAGE_ENVELOPE, STAGE_FLOOR, STAGE_PEAKS, STAGE_ALL = 1, 2, 4, 7
 F_STATIC_FLOOR, F_DRAFT_FLOOR, F_NAN_FLOOR, F_TOO_SHORT, F_BAD_WINDOW = 1, 2, 4, 8, 16
 F_TROUGH_TIE, F_PEAK_TIE = 32, 64      # decisive height tie in find_peaks' distance filter (bpmx.h)
@@ -38,6 +38,7 @@ OPT_HILBERT_BLUESTEIN = 4096
 OPT_REF_NOSPLIT = 8192
 OPT_BEATS_GLOBAL = 16384           # bpmx_beats_device, through bpmx_set_options (test/diagnostic)
 OPT_METRICS_GLOBAL = 32768         # bpmx_metrics_device, through bpmx_set_options (test/diagnostic)
+OPT_RECT_SEQ = 65536               # rectified mode: the pandas recursion for every recording (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS

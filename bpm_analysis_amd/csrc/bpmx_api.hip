@@ -432,6 +432,7 @@ int bpmx_run_ordered(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, c
 int bpmx_run(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O, void *stream) {
     int rc;
     if (ctx && P && B && O && !ctx->root && ctx->pipe_chunks >= 2 && B->n_files >= 2 * ctx->pipe_chunks &&
+        P->mode != BPMX_MODE_RECTIFIED &&        /* rectified mode is not pipelined */
         (P->stages & BPMX_STAGE_ENVELOPE) && (P->stages & (BPMX_STAGE_FLOOR | BPMX_STAGE_PEAKS)) &&
         B->frame_offsets && B->pcm && O->env && O->n_troughs && O->n_peaks && O->flags)
         rc = run_pipelined(ctx, P, B, O, (hipStream_t)stream);

@@ -13,6 +13,8 @@
 #include <stdint.h>
 
 #include "../../include/bpmx.h"
+#include "bpmx_pcm.h"
+#include "bpmx_rollmean.h"   /* win_bounds, RollMean */
 
 #define BPMX_WAVE 64
 
@@ -21,37 +23,7 @@ namespace bpmx {
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
-/* ---- PCM access ------------------------------------------------------- */
-/* numpy dtype of x after `np.mean(axis=1)` (bpm_analysis.py:1015-1016):
- * mono keeps its dtype, multi-channel ints -> f64, f32 -> f32. */
-__host__ __device__ __forceinline__ int work_dtype(int dtype, int channels) {
-    if (channels <= 1) return dtype;
-    return dtype == BPMX_DT_F32 ? BPMX_DT_F32 : BPMX_DT_F64;
-}
-
-__device__ __forceinline__ double load_pcm(const void *pcm, int dtype, int64_t idx) {
-    switch (dtype) {
-    case BPMX_DT_U8: return (double)((const uint8_t *)pcm)[idx];
-    case BPMX_DT_I16: return (double)((const int16_t *)pcm)[idx];
-    case BPMX_DT_I32: return (double)((const int32_t *)pcm)[idx];
-    case BPMX_DT_F32: return (double)((const float *)pcm)[idx];
-    default: return ((const double *)pcm)[idx];
-    }
-}
-
-/* value of frame `frame` after the channel mean */
-__device__ __forceinline__ double frame_value(const void *pcm, int dtype, int channels, int64_t frame) {
-    if (channels <= 1) return load_pcm(pcm, dtype, frame);
-    if (dtype == BPMX_DT_F32) {
-        const float *p = (const float *)pcm + frame * channels;
-        float s = p[0];
-        for (int c = 1; c < channels; ++c) s = s + p[c];
-        return (double)(s / (float)channels);
-    }
-    double s = load_pcm(pcm, dtype, frame * channels);
-    for (int c = 1; c < channels; ++c) s = s + load_pcm(pcm, dtype, frame * channels + c);
-    return s / (double)channels;
-}
+/* ---- PCM access: work_dtype, load_pcm, frame_value in bpmx_pcm.h ---- */
 
 /* scipy odd_ext (_arraytools.py:57-107): 2*end - v evaluated in the working
  * dtype, i.e. with integer wraparound or float32 rounding. */
@@ -107,14 +79,6 @@ __device__ __forceinline__ double interp_at(int64_t x, const TP *t, VF v, int m)
         if (r != r && y0 == y1) r = y0;
     }
     return r;
-}
-
-/* pandas centered fixed window (pandas/core/indexers/objects.py:93-120) */
-__host__ __device__ __forceinline__ void win_bounds(int64_t i, int64_t n, int64_t w, int64_t &s, int64_t &e) {
-    int64_t off = (w - 1) / 2;
-    int64_t ee = i + 1 + off, ss = ee - w;
-    e = ee < 0 ? 0 : (ee > n ? n : ee);
-    s = ss < 0 ? 0 : (ss > n ? n : ss);
 }
 
 /* ---- wave / block primitives (64-lane) -------------------------------- */

@@ -581,6 +581,40 @@ struct MetricsArgs {
 };
 __global__ void k_metrics(MetricsArgs A);
 
+/* Rectified-mode envelope (k_rect.hip): the centred rolling mean of |x| at the
+ * native rate.  Integer PCM of one or two channels takes the exact-integer
+ * route (window sums from int64 prefix sums, one division); everything else
+ * the pandas recursion, one lane per recording.  bpmx_plan.h rect_plan picks
+ * the route and sizes the launches. */
+constexpr int RECT_T = 256;                 /* threads per workgroup, every rect kernel */
+constexpr int64_t RECT_CHUNK = 2048;        /* outputs per workgroup, and inputs per chunk sum */
+constexpr int64_t RECT_LDS_N = 7936;        /* prefix entries a workgroup keeps in LDS: 31 per thread (62 KB as
+                                               int64 for int32 PCM, 31 KB as int32 for u8 / int16) */
+struct RectArgs {
+    const void *pcm;
+    const int64_t *foff;   /* [F+1] frame offsets */
+    const int64_t *doff;   /* [F+1] output offsets (no decimation: the recording lengths again) */
+    const int32_t *active; /* [F] */
+    int32_t n_files, dtype, channels, window;
+    double *env;           /* [sum N] */
+    int64_t *csum;         /* global-prefix variant: [F][nch] chunk sums, scanned in place */
+    int64_t nch;           /* chunks of the longest recording */
+    double *rows;          /* general route: the rectified values as rows [frame][recording] */
+};
+/* exact-integer route, LDS variant (window + RECT_CHUNK <= RECT_LDS_N): grid (chunks, F), dynamic LDS */
+template <int DT, bool STEREO>
+__global__ void k_rect_lds(RectArgs A);
+/* exact-integer route, global-prefix variant, three stream-ordered launches:
+ * chunk sums (chunks, F), their exclusive scan per recording (F), outputs (chunks, F) */
+template <int DT, bool STEREO>
+__global__ void k_rect_csum(RectArgs A);
+__global__ void k_rect_cscan(RectArgs A);
+template <int DT, bool STEREO>
+__global__ void k_rect_gout(RectArgs A);
+/* general route: gather into rows (frame tiles of 64, recording tiles of 64), then one lane per recording */
+__global__ void k_rect_pick(RectArgs A);
+__global__ void k_rect_seq(RectArgs A);
+
 }  // namespace bpmx
 
 #endif

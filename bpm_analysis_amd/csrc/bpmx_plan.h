@@ -13,6 +13,7 @@
 
 #include "bpmx_beats_core.h"
 #include "bpmx_metrics_core.h"
+#include "bpmx_rect_core.h"
 #include "bpmx_kernels.h"
 
 namespace bpmx {
@@ -183,6 +184,66 @@ inline RefEnvPlan ref_env_plan(int64_t maxnd, int32_t env_window, int32_t option
     if (R.chain && R.wants_split && maxnd >= 4096) {
         for (int k = 1; k <= 3; ++k) R.kend[R.nkc++] = (maxnd - (maxnd >> k)) & ~(int64_t)63;
         R.kend[R.nkc++] = maxnd;
+    }
+    return R;
+}
+
+/* Rectified-mode envelope (k_rect.hip): the route and its launch geometry.
+ *
+ * Exact-integer route.  For u8 / i16 / i32 PCM of one or two channels the
+ * rectified frame a[i] (2 a[i] for two channels, bpmx_rect_core.h) is an
+ * integer of magnitude at most 2^32.  pandas' roll_mean only ever holds sums
+ * of at most w such values in its Kahan add/remove recursion, so while
+ * w * 2^32 < 2^53 (w <= RECT_W_EXACT_MAX) every partial sum is exactly
+ * representable, both compensation terms stay 0, and the running sum is the
+ * exact window sum (+0.0 when it is zero).  calc_mean's corrections are then
+ * no-ops: a run of equal values returns prev, which is the exact quotient;
+ * neg_ct == 0 with a negative result and neg_ct == nobs with a positive one
+ * cannot happen with an exact sum.  So env[i] = (double)S_i [* 0.5] / nobs_i
+ * with S_i the int64 window sum: no sequential pass, S_i from prefix sums.
+ *   LDS variant (chunk + w <= RECT_LDS_N): one workgroup per chunk of outputs
+ *     loads the chunk and its halo, scans in LDS and writes the outputs.
+ *   Global-prefix variant (longer windows): per-chunk sums, an exclusive scan
+ *     of each recording's chunk sums, then a pass that rebuilds the chunk-
+ *     local prefixes around the window ends and starts.  Three stream-ordered
+ *     launches; no workgroup waits on another.
+ * General route (f32 / f64, more than two channels, a window beyond the bound,
+ * BPMX_OPT_RECT_SEQ): the pandas recursion, one lane per recording, over rows
+ * gathered as [frame][recording]. */
+enum { RECT_INT_LDS = 0, RECT_INT_GLOBAL = 1, RECT_GENERAL = 2 };
+
+struct RectPlan {
+    int route;
+    bool integer;               /* the exact-integer route (either variant) */
+    int64_t chunk;              /* outputs per workgroup; inputs per chunk sum */
+    int64_t nch;                /* chunks of the longest recording */
+    size_t lds;                 /* dynamic LDS bytes of k_rect_lds / k_rect_gout: 4 per prefix entry, 8 for int32 PCM */
+    size_t csum_bytes;          /* global-prefix variant: the chunk-sum table [F][nch] */
+    size_t rows_bytes;          /* general route: the row scratch [64-padded frames][F] */
+    dim3 grid;                  /* integer route: (nch, F) */
+    dim3 g_pick, g_seq;         /* general route */
+};
+
+inline RectPlan rect_plan(int dtype, int channels, int64_t w, int32_t options, int F, int64_t maxn) {
+    RectPlan R{};
+    R.chunk = RECT_CHUNK;
+    R.nch = std::max<int64_t>(1, (maxn + R.chunk - 1) / R.chunk);
+    R.integer = dtype <= BPMX_DT_I32 && channels <= 2 && w <= RECT_W_EXACT_MAX && !(options & BPMX_OPT_RECT_SEQ);
+    R.grid = dim3((unsigned)R.nch, (unsigned)F);
+    const size_t entry = dtype == BPMX_DT_I32 ? 8 : 4;       /* a workgroup's local prefix sums (k_rect.hip RPcm) */
+    if (!R.integer) {
+        R.route = RECT_GENERAL;
+        const int64_t rows = (maxn + 63) / 64 * 64;
+        R.rows_bytes = (size_t)rows * (size_t)F * 8;
+        R.g_pick = dim3((unsigned)(rows / 64), (unsigned)((F + 63) / 64));
+        R.g_seq = dim3((unsigned)((F + 63) / 64));
+    } else if (R.chunk + w <= RECT_LDS_N) {
+        R.route = RECT_INT_LDS;
+        R.lds = (size_t)std::min<int64_t>(R.chunk + w, maxn + 1) * entry;    /* prefix entries 0 .. inputs */
+    } else {
+        R.route = RECT_INT_GLOBAL;
+        R.lds = (size_t)(2 * R.chunk) * entry;
+        R.csum_bytes = (size_t)F * (size_t)R.nch * 8;
     }
     return R;
 }

@@ -4,7 +4,7 @@
  *
  * Stage order follows analyze_wav_file (bpm_analysis.py:1731-1732) and the
  * classifier's raw-peak call (:89 -> :223-229):
- *   ENVELOPE  k_envelope_ref | native kernels (k_envelope_native.hip)
+ *   ENVELOPE  k_envelope_ref | native kernels (k_envelope_native.hip) | k_rect_* (rectified mode)
  *   FLOOR     k_block_stats, k_quantile, k_find_peaks(-env), k_interp,
  *             k_rolling_quantile (draft), k_sanitize, k_interp,
  *             k_rolling_quantile (final), k_floor_final
@@ -117,7 +117,8 @@ struct Run {
 int check_args(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O) {
     if (!ctx || !P || !B || !O) return fail(BPMX_E_ARG, "NULL argument");
     if (B->n_files < 1 || !B->frame_offsets) return fail(BPMX_E_ARG, "empty batch");
-    if (P->mode != BPMX_MODE_REFERENCE && P->mode != BPMX_MODE_NATIVE) return fail(BPMX_E_ARG, "bad mode");
+    if (P->mode != BPMX_MODE_REFERENCE && P->mode != BPMX_MODE_NATIVE && P->mode != BPMX_MODE_RECTIFIED)
+        return fail(BPMX_E_ARG, "bad mode");
     if (P->dtype < BPMX_DT_U8 || P->dtype > BPMX_DT_F64) return fail(BPMX_E_ARG, "bad dtype");
     if (P->channels < 1 || P->ds < 1 || P->sr < 1) return fail(BPMX_E_ARG, "bad channels/ds/sr");
     const int st = P->stages;
@@ -131,6 +132,11 @@ int check_args(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const b
     if ((do_floor || do_peaks) && P->distance < 1) return fail(BPMX_E_ARG, "`distance` must be greater or equal to 1");
     if (do_floor && P->min_periods < 1) return fail(BPMX_E_ARG, "min_periods must be >= 1");
     if (do_env && P->env_window < 1) return fail(BPMX_E_ARG, "envelope window must be >= 1");
+    if (P->mode == BPMX_MODE_RECTIFIED) {
+        /* the envelope of the samples as they are: no decimation, no filtered signal */
+        if (P->ds != 1) return fail(BPMX_E_ARG, "rectified mode: ds must be 1");
+        if (O->y) return fail(BPMX_E_ARG, "rectified mode has no filtered signal: out.y must be NULL");
+    }
     return BPMX_OK;
 }
 
@@ -150,7 +156,8 @@ int build_geometry(Run &R, std::vector<int64_t> &boff) {
         G.doff[f + 1] = G.doff[f] + nd;
         boff[f + 1] = boff[f] + (nd + 63) / 64;
         G.maxnd = std::max(G.maxnd, nd);
-        const bool ok = (R.do_env || R.env_active) ? nd > 15 : nd >= 1;
+        /* rectified mode has no filtfilt pad: active like a run that starts from env */
+        const bool ok = ((R.do_env || R.env_active) && P->mode != BPMX_MODE_RECTIFIED) ? nd > 15 : nd >= 1;
         G.active[f] = ok ? 1 : 0;
         if (nd >= (int64_t)INT_MAX / 2) return fail(BPMX_E_LIMIT, "recording too long");
     }
@@ -236,7 +243,7 @@ int init_outputs(Run &R) {
     io.runs = G.d_run1;
     io.nraw = G.d_nraw == R.O->n_raw_troughs ? G.d_nraw : nullptr;       /* the caller's raw-trough counts */
     io.z1 = R.draft_masks; io.z2 = D.bounds ? R.draft_vfl + 2 * F : nullptr; io.z3 = R.fp_scan;
-    const bool init_in_carry = R.do_env && R.P->mode != BPMX_MODE_REFERENCE;
+    const bool init_in_carry = R.do_env && R.P->mode == BPMX_MODE_NATIVE;
     if (!init_in_carry) LAUNCH(ctx, G.s, "k_init_out", k_init_out, dim3((F + 255) / 256), dim3(256), 0, G.s, io);
     return BPMX_OK;
 }
@@ -414,9 +421,56 @@ int envelope_ref(Run &R) {
     return E.chain ? ref_means(R, E, nkc, a) : BPMX_OK;
 }
 
+/* ---- ENVELOPE, rectified mode ---- */
+
+struct RectKernels {
+    void (*lds)(RectArgs);
+    void (*csum)(RectArgs);
+    void (*gout)(RectArgs);
+};
+template <int DT>
+RectKernels rect_kernels(bool stereo) {
+    if (stereo) return {k_rect_lds<DT, true>, k_rect_csum<DT, true>, k_rect_gout<DT, true>};
+    return {k_rect_lds<DT, false>, k_rect_csum<DT, false>, k_rect_gout<DT, false>};
+}
+
+/* the route and its geometry are rect_plan's (bpmx_plan.h, with the argument
+ * for the exact-integer route) */
+int envelope_rect(Run &R) {
+    bpmx_ctx *ctx = R.ctx; const bpmx_params *P = R.P; const RunGeo &G = R.G; hipStream_t s = G.s; const int F = G.F;
+    int rc = BPMX_OK;
+    const RectPlan E = rect_plan(P->dtype, P->channels, P->env_window, P->options, F, G.maxnd);
+    RectArgs a{};
+    a.pcm = R.B.pcm; a.foff = G.d_foff; a.doff = G.d_doff; a.active = G.d_active;
+    a.n_files = F; a.dtype = P->dtype; a.channels = P->channels; a.window = P->env_window;
+    a.env = R.O->env; a.nch = E.nch;
+    if (E.route == RECT_GENERAL) {
+        a.rows = (double *)ctx->buf("rect_rows", E.rows_bytes, &rc);
+        if (rc != BPMX_OK) return rc;
+        LAUNCH(ctx, s, "k_rect_pick", k_rect_pick, E.g_pick, dim3(256), 0, s, a);
+        LAUNCH(ctx, s, "k_rect_seq", k_rect_seq, E.g_seq, dim3(64), 0, s, a);
+        return BPMX_OK;
+    }
+    const bool stereo = P->channels == 2;
+    const RectKernels K = P->dtype == BPMX_DT_U8    ? rect_kernels<BPMX_DT_U8>(stereo)
+                          : P->dtype == BPMX_DT_I16 ? rect_kernels<BPMX_DT_I16>(stereo)
+                                                    : rect_kernels<BPMX_DT_I32>(stereo);
+    if (E.route == RECT_INT_LDS) {
+        LAUNCH(ctx, s, "k_rect_lds", K.lds, E.grid, dim3(RECT_T), E.lds, s, a);
+        return BPMX_OK;
+    }
+    a.csum = (int64_t *)ctx->buf("rect_csum", E.csum_bytes, &rc);
+    if (rc != BPMX_OK) return rc;
+    LAUNCH(ctx, s, "k_rect_csum", K.csum, E.grid, dim3(RECT_T), 0, s, a);
+    LAUNCH(ctx, s, "k_rect_cscan", k_rect_cscan, dim3(F), dim3(RECT_T), 0, s, a);
+    LAUNCH(ctx, s, "k_rect_gout", K.gout, E.grid, dim3(RECT_T), E.lds, s, a);
+    return BPMX_OK;
+}
+
 int envelope_stage(Run &R) {
     StageRange range("bpmx:envelope");
     if (R.P->mode == BPMX_MODE_REFERENCE) return envelope_ref(R);
+    if (R.P->mode == BPMX_MODE_RECTIFIED) return envelope_rect(R);
     const bool detect = R.D.do_floor || R.D.do_peaks;
     int rc = native_envelope(R.ctx, R.P, &R.B, R.O, R.G, detect ? &R.qa : nullptr, &R.io);
     if (rc != BPMX_OK) return rc;

@@ -9,7 +9,8 @@ pixeru/bpm_analysis (bpm_analysis.py):
   (the body of ``PeakClassifier._find_raw_peaks``)
 
 plus the batch entry points the reference lacks (``analyze_batch``,
-``analyze_wav_files``) and
+``analyze_wav_files``), the labeler's envelope of a filtered WAV
+(``labeler_envelope``, heartbeat_labeler.py:53-67) and
 ``patch_reference(module)``, which rebinds an imported reference module's
 three hot-path functions to these so its unchanged ``analyze_wav_file``
 (and therefore gui.py / main.py / the Gradio app) runs on the GPU.
@@ -28,8 +29,11 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .design import design
-from .engine import default_detector
+from .config import DEFAULT_PARAMS
+from .engine import default_detector, mode_design
+
+RECTIFIED = "rectified"
+NO_DEBUG_WAV_MSG = "Rectified mode reads an already filtered WAV: 'save_filtered_wav' is ignored."
 
 PADLEN_MSG = "The length of the input vector x must be greater than padlen, which is 15."
 DISTANCE_MSG = "`distance` must be greater or equal to 1"          # scipy find_peaks (:1070, :227)
@@ -132,16 +136,23 @@ def preprocess_audio(file_path: str, params: Dict, output_directory: str, mode: 
 
     ``mode`` (or ``params["bpmx_mode"]`` when called through the reference's
     unchanged ``analyze_wav_file``): "reference" (default, bit-exact with the
-    shipped pipeline) or "native" (sosfiltfilt at fs -> decimate -> |hilbert|).
+    shipped pipeline), "native" (sosfiltfilt at fs -> decimate -> |hilbert|) or
+    "rectified" (the file is an already filtered WAV: the labeler's envelope
+    |x| -> rolling mean at the file's own rate; no filter, so no debug WAV, no
+    padlen error and no Nyquist check).
     The noise floor, troughs and raw peaks of the same recording are computed
     in the same GPU run and kept for the calls that follow (see _LastRecording)."""
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
+    rect = mode == RECTIFIED
     save_debug_file = params["save_filtered_wav"]
+    if rect and save_debug_file:
+        logging.info(NO_DEBUG_WAV_MSG)
+        save_debug_file = False
     sample_rate, audio = _read_wav(file_path)
-    d = design(sample_rate, params)
+    d = mode_design(sample_rate, params, mode, log=True)
     n = audio.shape[0]
-    if -(-n // d.ds) <= 15:
+    if not rect and -(-n // d.ds) <= 15:
         raise ValueError(PADLEN_MSG)
     _last.rec = None
     stages = N.STAGE_ALL if d.distance >= 1 else N.STAGE_ENVELOPE     # distance < 1 raises in the later calls
@@ -216,6 +227,16 @@ def find_raw_peaks(audio_envelope: np.ndarray, sample_rate: int, params: Dict, h
     return peaks
 
 
+def labeler_envelope(file_path: str, device: int = 0) -> Tuple[np.ndarray, int]:
+    """The envelope heartbeat_labeler.py:53-67 shows for a filtered WAV, on the
+    GPU: channel mean, ``np.abs``, the centred pandas rolling mean over
+    ``sample_rate // 10`` samples, bit for bit -> (envelope, sample_rate)."""
+    sample_rate, audio = _read_wav(file_path)
+    r = default_detector(device).run_host([audio], sample_rate, DEFAULT_PARAMS, mode=RECTIFIED,
+                                          stages=N.STAGE_ENVELOPE)[0]
+    return np.array(r["env"]), sample_rate
+
+
 def detect(pcm: np.ndarray, fs: int, params: Dict, mode: str = "reference", device: int = 0) -> dict:
     """The whole hot path for one in-memory recording -> dict(env, floor, troughs, peaks, sr, flags)."""
     return analyze_batch([pcm], fs, params, mode=mode, device=device)[0]
@@ -229,7 +250,7 @@ def analyze_batch(recordings: Sequence[np.ndarray], fs: int, params: Dict, mode:
     A recording too short for filtfilt (Nd <= 15) comes back with
     ``flags & F_TOO_SHORT`` and no outputs instead of failing the batch.
     """
-    design(fs, params)   # Nyquist check / clamp warnings once per batch
+    mode_design(fs, params, mode, log=True)   # Nyquist check / clamp warnings once per batch (none when rectified)
     return default_detector(device).run_host(list(recordings), fs, params, mode=mode, stages=N.STAGE_ALL,
                                              resolve_ties=True)
 
@@ -250,7 +271,11 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
     raise for that file, e.g. the filtfilt padlen ValueError)."""
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
+    rect = mode == RECTIFIED
     save = bool(params.get("save_filtered_wav", False))
+    if rect and save:
+        logging.info(NO_DEBUG_WAV_MSG)
+        save = False
     out: List[dict] = [None] * len(file_paths)
     groups: Dict[tuple, List[int]] = {}
     audio = []
@@ -267,7 +292,7 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
     det = default_detector(device)
     for (fs, _, _), idx in groups.items():
         try:
-            d = design(fs, params)                    # clamp warnings / Nyquist ValueError, once per group
+            d = mode_design(fs, params, mode, log=True)   # clamp warnings / Nyquist ValueError, once per group
         except ValueError as exc:
             for k in idx:
                 out[k] = {"error": exc}
@@ -281,7 +306,7 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
             for k in idx:                             # (a too-short file fails first, in filtfilt)
-                short = -(-audio[k][1].shape[0] // d.ds) <= 15
+                short = not rect and -(-audio[k][1].shape[0] // d.ds) <= 15
                 out[k] = {"error": ValueError(PADLEN_MSG) if short else exc}
             continue
         for k, r in zip(idx, res):
@@ -332,7 +357,11 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     names = list(file_paths) if original_file_paths is None else list(original_file_paths)
     if len(hints) != n or len(names) != n:
         raise ValueError("start_bpm_hints and original_file_paths need one entry per file")
+    rect = mode == RECTIFIED
     save = bool(params.get("save_filtered_wav", False))
+    if rect and save:
+        logging.info(NO_DEBUG_WAV_MSG)
+        save = False
     out: List[dict] = [None] * n
     groups: Dict[tuple, List[int]] = {}
     audio = []
@@ -348,7 +377,7 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     det = default_detector(device)
     for (fs, _, _), idx in groups.items():
         try:
-            d = design(fs, params)                    # clamp warnings / Nyquist ValueError, once per group
+            d = mode_design(fs, params, mode, log=True)   # clamp warnings / Nyquist ValueError, once per group
         except ValueError as exc:
             for k in idx:
                 out[k] = {"error": exc}
@@ -356,13 +385,14 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
         try:
             if d.distance < 1:
                 raise ValueError(DISTANCE_MSG)
-            res = det.run_host_reports([audio[k][1] for k in idx], fs, params, mode=mode,
+            run_params = dict(params, save_filtered_wav=False) if rect else params
+            res = det.run_host_reports([audio[k][1] for k in idx], fs, run_params, mode=mode,
                                        hints=[hints[k] for k in idx], plot=plot)
         except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
             for k in idx:                             # (a too-short file fails first, in filtfilt)
-                short = -(-audio[k][1].shape[0] // d.ds) <= 15
+                short = not rect and -(-audio[k][1].shape[0] // d.ds) <= 15
                 out[k] = {"error": ValueError(PADLEN_MSG) if short else exc}
             continue
         for k, r in zip(idx, res):

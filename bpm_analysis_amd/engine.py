@@ -21,7 +21,22 @@ import numpy as np
 from . import _native as N
 from .design import Design, design, detect_design, dtype_code, make_params
 
-MODES = {"reference": N.MODE_REFERENCE, "native": N.MODE_NATIVE}
+MODES = {"reference": N.MODE_REFERENCE, "native": N.MODE_NATIVE, "rectified": N.MODE_RECTIFIED}
+
+
+def mode_design(fs: int, params: dict, mode: str = "reference", log: bool = False) -> Design:
+    """The host derivations a run in `mode` needs.  Rectified mode takes the
+    samples as they are (heartbeat_labeler.py:53-67): ``detect_design`` at
+    `fs`, so ds 1, sr fs, no filter design, no Nyquist check and no clamp
+    warnings; the other modes ``design``."""
+    if mode == "rectified":
+        return detect_design(fs, params)
+    return design(fs, params, log=log)
+
+
+def _no_filtered_signal(mode: str, wanted: bool) -> None:
+    if wanted and mode == "rectified":
+        raise N.BpmxArgError("rectified mode has no filtered signal: y / y16 cannot be requested", N.E_ARG)
 
 
 def _torch():
@@ -548,8 +563,9 @@ class Detector:
         ENVELOPE is not requested and `out.env` already holds the envelopes).
         `order`: bpmx_run_ordered's candidate export / visiting ranks (see
         ``resolve_ties``)."""
+        _no_filtered_signal(mode, want_y or (out is not None and out.y is not None))
         if d is None:
-            d = design(fs, params, log=log)
+            d = mode_design(fs, params, mode, log=log)
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64)
         if out is None:
             out = self.alloc(fo, d.ds, d.sr, want_y=want_y)
@@ -925,7 +941,8 @@ class Detector:
         fo = np.zeros(len(recordings) + 1, dtype=np.int64)
         fo[1:] = np.cumsum([r.shape[0] for r in recordings])
         host = np.concatenate([np.ascontiguousarray(r).reshape(-1) for r in recordings])
-        d = design(fs, params, log=False)
+        _no_filtered_signal(mode, want_y)
+        d = mode_design(fs, params, mode)
         pcm = torch.from_numpy(host).to(self.device)
         res = self.run(pcm, fo, fs, params, mode=mode, stages=stages, channels=ch, want_y=want_y, d=d,
                        options=options)

@@ -47,6 +47,8 @@
 extern "C" {
 #endif
 
+/* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
+ * BPMX_OPT_RECT_SEQ. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
@@ -56,8 +58,25 @@ enum bpmx_dtype { BPMX_DT_U8 = 0, BPMX_DT_I16 = 1, BPMX_DT_I32 = 2, BPMX_DT_F32 
  *            decimated rate, rolling-mean envelope; bpm_analysis.py:1031-1054).
  * NATIVE:    the north_star ordering (sosfiltfilt at the native rate -> pick
  *            -> |Hilbert| -> rolling mean); envelope within 1e-9 relative of the
- *            scipy composition, detection stages identical. */
-enum bpmx_mode { BPMX_MODE_REFERENCE = 0, BPMX_MODE_NATIVE = 1 };
+ *            scipy composition, detection stages identical.
+ * RECTIFIED: the labeler's envelope of an already filtered WAV, bit-exact
+ *            (heartbeat_labeler.py:48-67): the frame value as in the other
+ *            modes, np.abs in its dtype (the most negative int16 / int32 stays
+ *            itself, u8 is unchanged), no decimation and no filter, then
+ *            pd.Series(a).rolling(fs // 10, min_periods=1, center=True).mean()
+ *            with +-inf counted as NaN.  Rules of the mode:
+ *              - ds must be 1 (sr == fs, Nd == N), else BPMX_E_ARG;
+ *              - out.y must be NULL (there is no filtered signal), else BPMX_E_ARG;
+ *              - a recording is active when it has >= 1 frame, as in a run that
+ *                starts from env; there is no filtfilt pad, so BPMX_F_TOO_SHORT
+ *                only marks an empty recording;
+ *              - FLOOR and PEAKS run unchanged on that envelope at rate fs, with
+ *                the limits of an env-level run of the same length and window;
+ *              - bpmx_set_pipeline does not apply: the run is not pipelined.
+ *            Integer PCM of one or two channels is computed from exact int64
+ *            window sums in parallel; other inputs by the pandas recursion, one
+ *            lane per recording (only meant to be right). */
+enum bpmx_mode { BPMX_MODE_REFERENCE = 0, BPMX_MODE_NATIVE = 1, BPMX_MODE_RECTIFIED = 2 };
 
 enum bpmx_stage {
     BPMX_STAGE_ENVELOPE = 1, /* PCM -> env (and y)        */
@@ -136,9 +155,12 @@ enum bpmx_option {
     BPMX_OPT_BEATS_GLOBAL = 16384,   /* bpmx_beats_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS for the tables that fit
                                         there (test/diagnostic) */
-    BPMX_OPT_METRICS_GLOBAL = 32768  /* bpmx_metrics_device (set with bpmx_set_options): every recording's
+    BPMX_OPT_METRICS_GLOBAL = 32768, /* bpmx_metrics_device (set with bpmx_set_options): every recording's
                                         workspace in global memory, the curve and beats read where they lie
                                         (test/diagnostic) */
+    BPMX_OPT_RECT_SEQ = 65536        /* rectified mode: the general route (the pandas recursion, one lane per
+                                        recording) for every recording, also where the exact-integer route
+                                        applies (test/diagnostic) */
 };
 
 /* bpmx_stats counters of the last run with BPMX_OPT_STATS */
