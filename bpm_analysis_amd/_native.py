@@ -39,6 +39,7 @@ OPT_REF_NOSPLIT = 8192
 OPT_BEATS_GLOBAL = 16384           # bpmx_beats_device, through bpmx_set_options (test/diagnostic)
 OPT_METRICS_GLOBAL = 32768         # bpmx_metrics_device, through bpmx_set_options (test/diagnostic)
 OPT_RECT_SEQ = 65536               # rectified mode: the pandas recursion for every recording (test/diagnostic)
+OPT_LABELS_GLOBAL = 131072          # bpmx_labels_device, through bpmx_set_options (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS
@@ -47,6 +48,10 @@ METRICS_OK, METRICS_TIE, METRICS_E_DISTANCE, METRICS_NONE, METRICS_OVERFLOW = 0,
 # bpmx_metrics_out.record (16 doubles per file, NaN = absent)
 MR_AVG_BPM, MR_MIN_BPM, MR_MAX_BPM, MR_AVG_RMSSDC, MR_AVG_SDNN = 0, 1, 2, 3, 4
 MR_HRR_PEAK, MR_HRR_RECOVERY_BPM, MR_HRR_VALUE, MR_RECOVERY, MR_EXERTION, METRICS_RECORD = 5, 6, 7, 8, 12, 16
+# bpmx_labels_out.status, the label types and .record (4 doubles per file)
+LABELS_OK, LABELS_NONE, LABELS_OVERFLOW = 0, -20, -21
+LABEL_S1, LABEL_S2 = 1, 2
+LR_AVG_DT, LR_AVG_BPM, LR_N_S1, LR_N_S2, LABELS_RECORD = 0, 1, 2, 3, 4
 # bpmx_trace_out.record (bpmx_trace_field: 18 doubles per raw peak), .code (bpmx_trace_code) and .gap
 TR_BLEND, TR_BASE_CONF, TR_STAB_FACTOR, TR_STAB_RATIO, TR_ADJ_AMOUNT, TR_ADJ_RATIO, TR_ADJ_RMAX = 0, 1, 2, 3, 4, 5, 6
 TR_IV_AMOUNT, TR_IV_GAP, TR_IV_CAP, TR_FINAL = 7, 8, 9, 10
@@ -58,7 +63,8 @@ TR_GAP_NONE, TR_GAP_S1, TR_GAP_S2 = 0, 1, 2
 EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy", "bpmx_decimated_length",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
            "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
-           "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot"]
+           "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot",
+           "bpmx_labels_device"]
 
 
 class Params(ctypes.Structure):
@@ -136,6 +142,19 @@ class MetricsOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in (
         "hrv_time", "hrv_rmssdc", "hrv_sdnn", "hrv_bpm", "n_hrv", "inc_a", "inc_b", "dec_a", "dec_b",
         "inc_slope", "inc_dur", "dec_slope", "dec_dur", "n_inc", "n_dec", "record", "status")]
+
+
+class LabelParams(ctypes.Structure):
+    """bpmx_label_params: the gap that separates two groups of S1 marks."""
+    _fields_ = [("gap_sec", ctypes.c_double)]
+
+
+class LabelsOut(ctypes.Structure):
+    """bpmx_labels_out: the device arrays bpmx_labels_device fills (per-file
+    slices at pk_off[f]; every pointer required)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "lb_pos", "lb_type", "lb_time", "lb_bpm", "pr_s1", "pr_s2", "pr_dt", "gr_id", "gr_first", "gr_last",
+        "gr_s1", "gr_pairs", "gr_dt", "gr_bpm", "n_labels", "n_pairs", "n_groups", "record", "status")]
 
 
 class BpmxError(RuntimeError):
@@ -228,6 +247,10 @@ def load() -> ctypes.CDLL:
         L.bpmx_pack_plot.argtypes = [P, I32, ctypes.POINTER(ctypes.c_int64), I32, I32, ctypes.POINTER(Out), P, P,
                                      I64, P]
         L.bpmx_pack_plot.restype = ctypes.c_int
+    if hasattr(L, "bpmx_labels_device"):
+        L.bpmx_labels_device.argtypes = [P, I32, I32, ctypes.POINTER(LabelParams), ctypes.POINTER(PackedOut),
+                                         ctypes.POINTER(BeatsOut), P, ctypes.POINTER(LabelsOut), P]
+        L.bpmx_labels_device.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

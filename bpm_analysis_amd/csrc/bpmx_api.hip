@@ -2,7 +2,7 @@
  * bpmx_api.hip — host side of the C ABI (include/bpmx.h): context, scratch,
  * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
  * bpmx_pack_trough_floor, bpmx_pack_plot, bpmx_beats_device,
- * bpmx_beats_device_ex and bpmx_metrics_device.
+ * bpmx_beats_device_ex, bpmx_metrics_device and bpmx_labels_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -99,6 +99,25 @@ int metrics_stage(bpmx_ctx *ctx, const MetricsPlan &M, int32_t n_files, int32_t 
         if (rc != BPMX_OK) return rc;
     }
     LAUNCH(ctx, s, "k_metrics", k_metrics, dim3(M.grid), dim3(METRICS_T), M.lds, s, a);
+    return BPMX_OK;
+}
+
+/* the labels behind the traced beat stages: one launch sized by the plan */
+int labels_stage(bpmx_ctx *ctx, const LabelsPlan &L, int32_t n_files, int32_t sr, const bpmx_label_params &P,
+                 const bpmx_packed &t, const bpmx_beats_out &b, const int32_t *gap, const bpmx_labels_out &o,
+                 hipStream_t s) {
+    int rc = BPMX_OK;
+    LabelsArgs a{};
+    a.n_files = n_files; a.sr = sr; a.cap = t.cap_peaks; a.lds_n = L.lds_n; a.fixed = L.fixed;
+    a.pk_off = t.pk_off; a.pk_idx = t.pk_idx;
+    a.final_idx = b.final_idx; a.n_final = b.n_final; a.n_bpm = b.n_bpm; a.b_status = b.status;
+    a.bpm_t = b.bpm_t; a.bpm = b.bpm; a.tags = b.tags; a.gap = gap;
+    a.P = P; a.O = o;
+    if (L.any_global) {
+        a.gws = (unsigned char *)ctx->buf("labels_ws", L.gws, &rc);
+        if (rc != BPMX_OK) return rc;
+    }
+    LAUNCH(ctx, s, "k_labels", k_labels, dim3(L.grid), dim3(LABELS_T), L.lds, s, a);
     return BPMX_OK;
 }
 
@@ -670,6 +689,27 @@ int bpmx_metrics_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_m
     HIP_TRY(hipSetDevice(ctx->device));
     return metrics_stage(ctx, metrics_plan(n_files, tables->cap_peaks, ctx->options, params->hrv_window_size_beats),
                          n_files, sr, *params, epoch_us, *tables, *beats, *out, (hipStream_t)stream);
+}
+
+int bpmx_labels_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_label_params *params,
+                       const bpmx_packed *tables, const bpmx_beats_out *beats, const int32_t *gap,
+                       const bpmx_labels_out *out, void *stream) {
+    if (!ctx || !params || !tables || !beats || !gap || !out)
+        return fail(BPMX_E_ARG, "bpmx_labels_device: NULL argument (gap, the trace of bpmx_beats_device_ex, is required)");
+    if (n_files < 1 || sr < 1) return fail(BPMX_E_ARG, "bpmx_labels_device: bad n_files/sr");
+    if (!tables->pk_off || !tables->pk_idx || tables->cap_peaks < 0 || tables->cap_peaks >= (int64_t)INT_MAX)
+        return fail(BPMX_E_ARG, "bpmx_labels_device: needs pk_off, pk_idx and 0 <= cap_peaks < 2^31");
+    if (!beats->final_idx || !beats->n_final || !beats->bpm_t || !beats->bpm || !beats->n_bpm || !beats->tags ||
+        !beats->status)
+        return fail(BPMX_E_ARG, "bpmx_labels_device: the beats' final_idx, n_final, bpm_t, bpm, n_bpm, tags and "
+                                "status are required");
+    if (!out->lb_pos || !out->lb_type || !out->lb_time || !out->lb_bpm || !out->pr_s1 || !out->pr_s2 || !out->pr_dt ||
+        !out->gr_id || !out->gr_first || !out->gr_last || !out->gr_s1 || !out->gr_pairs || !out->gr_dt ||
+        !out->gr_bpm || !out->n_labels || !out->n_pairs || !out->n_groups || !out->record || !out->status)
+        return fail(BPMX_E_ARG, "bpmx_labels_device: every pointer of bpmx_labels_out is required");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return labels_stage(ctx, labels_plan(n_files, tables->cap_peaks, ctx->options), n_files, sr, *params, *tables,
+                        *beats, gap, *out, (hipStream_t)stream);
 }
 
 }  // extern "C"

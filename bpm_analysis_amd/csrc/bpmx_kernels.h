@@ -581,6 +581,25 @@ struct MetricsArgs {
 };
 __global__ void k_metrics(MetricsArgs A);
 
+/* bpmx_labels_device (k_labels.hip): one workgroup of LABELS_T threads per recording */
+enum { LABELS_T = 256 };
+struct LabelsArgs {
+    int32_t n_files, sr;
+    int64_t cap;                /* table capacity, entries */
+    int64_t lds_n;              /* recordings of at most this many peaks work in LDS (-1: none) */
+    size_t fixed;               /* labels_ws_fixed(LABELS_T): a global slice starts at f * fixed + LB_STRIDE * pk_off[f] */
+    const int64_t *pk_off;      /* [F+1] */
+    const int32_t *pk_idx;
+    const int32_t *final_idx, *n_final, *n_bpm, *b_status;   /* k_beats_trace's outputs */
+    const double *bpm_t, *bpm;
+    const int8_t *tags;
+    const int32_t *gap;
+    unsigned char *gws;         /* workspaces of the recordings beyond lds_n (bpmx_plan.h labels_plan) */
+    bpmx_label_params P;
+    bpmx_labels_out O;
+};
+__global__ void k_labels(LabelsArgs A);
+
 /* Rectified-mode envelope (k_rect.hip): the centred rolling mean of |x| at the
  * native rate.  Integer PCM of one or two channels takes the exact-integer
  * route (window sums from int64 prefix sums, one division); everything else

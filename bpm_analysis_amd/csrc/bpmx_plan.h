@@ -13,6 +13,7 @@
 
 #include "bpmx_beats_core.h"
 #include "bpmx_metrics_core.h"
+#include "bpmx_labels_core.h"
 #include "bpmx_rect_core.h"
 #include "bpmx_kernels.h"
 
@@ -311,6 +312,35 @@ inline MetricsPlan metrics_plan(int F, int64_t cap_peaks, int32_t options, int32
     M.fixed = metrics_ws_fixed(METRICS_T, M.fw);
     M.gws = M.any_global ? (size_t)F * M.fixed + (size_t)cap_peaks * MX_STRIDE : 0;
     return M;
+}
+
+/* bpmx_labels_device: one workgroup of LABELS_T threads per recording
+ * (k_labels).  A recording's workspace (bpmx_labels_core.h) lives in LDS when
+ * it fits LABELS_LDS_BUDGET: 40 KB, so four workgroups share a CU's 160 KB,
+ * and the 605 peaks a 60 s recording can have are inside it.  Longer tables
+ * take a slice of one global buffer at f * fixed + LB_STRIDE * pk_off[f].
+ * Sized like beats_plan from the capacity and the file count alone. */
+constexpr size_t LABELS_LDS_BUDGET = 40 * 1024;
+
+struct LabelsPlan {
+    unsigned grid;              /* workgroups: one per recording */
+    int64_t lds_n;              /* most peaks of an LDS-path recording (-1: every recording goes global) */
+    size_t lds;                 /* dynamic LDS bytes per workgroup */
+    bool any_global;
+    size_t fixed;               /* labels_ws_fixed(LABELS_T) */
+    size_t gws;                 /* bytes of the global workspace buffer (0: none) */
+};
+
+inline LabelsPlan labels_plan(int F, int64_t cap_peaks, int32_t options, size_t budget = LABELS_LDS_BUDGET) {
+    LabelsPlan L{};
+    L.grid = (unsigned)F;
+    const bool forced = (options & BPMX_OPT_LABELS_GLOBAL) != 0;
+    L.lds_n = forced ? -1 : std::min<int64_t>(cap_peaks, labels_ws_max_n(budget, LABELS_T));
+    L.lds = L.lds_n < 0 ? 0 : labels_ws_bytes(L.lds_n, LABELS_T);
+    L.any_global = cap_peaks > L.lds_n;
+    L.fixed = labels_ws_fixed(LABELS_T);
+    L.gws = L.any_global ? (size_t)F * L.fixed + (size_t)cap_peaks * LB_STRIDE : 0;
+    return L;
 }
 
 }  // namespace bpmx

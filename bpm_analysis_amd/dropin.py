@@ -322,7 +322,8 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
 
 def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output_directory: str,
                                  start_bpm_hints: Sequence = None, original_file_paths: Sequence[str] = None,
-                                 mode: str = None, device: int = 0, plot: bool = False) -> List[dict]:
+                                 mode: str = None, device: int = 0, plot: bool = False, labels: bool = False,
+                                 label_gap_sec: float = 5.0, labels_overwrite: bool = False) -> List[dict]:
     """``beats.analyze_wav_file`` for many WAV files with every stage on the
     device: per file ``<base>_bpm_plot.csv``, ``<base>_Analysis_Summary.md``,
     ``<base>_Debug_Log.md`` and ``<base>_Analysis_Settings.json`` (and both
@@ -344,12 +345,24 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     (``Metrics.to_host``).  ``start_bpm_hints``: one per file (None = none);
     ``original_file_paths`` name the reports (default: ``file_paths``).
 
+    With ``labels=True`` the labeler's output is made on the device as well
+    (``Detector.labels_device``: the analysis' final beats as S1 marks, its S2
+    marks, the S1-S2 pairs, the groups separated by pauses of
+    ``label_gap_sec`` and their statistics): each dict gains ``labels`` and
+    ``<base>_labels.csv`` is written as the labeler's ``save_labels`` writes it
+    (``labels.write_labels``), so the file opens in the labeler beside the CSV
+    and the debug WAV of the same run.  That file is where the labeler keeps
+    hand labels: an existing one is left as it is and the dict says
+    ``labels_written=False``, unless ``labels_overwrite=True``.  A file without
+    reports gets no label file.
+
     Returns one dict per path, in order: ``run_host_reports``' dict, or
     ``error`` with the exception the reference raises for that file; as there,
     a file with fewer than two final beats gets no reports
     (``final_metrics`` None)."""
     from .plot import write_plot_packed
     from .reports import write_reports_packed
+    from . import labels as LB
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
     n = len(file_paths)
@@ -387,7 +400,8 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                 raise ValueError(DISTANCE_MSG)
             run_params = dict(params, save_filtered_wav=False) if rect else params
             res = det.run_host_reports([audio[k][1] for k in idx], fs, run_params, mode=mode,
-                                       hints=[hints[k] for k in idx], plot=plot)
+                                       hints=[hints[k] for k in idx], plot=plot,
+                                       **(dict(labels=True, label_gap_sec=label_gap_sec) if labels else {}))
         except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
@@ -405,10 +419,15 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
             if "error" in r:                          # < 2 raw peaks (KeyError), scipy's ValueError in the metrics
                 out[k] = {"error": r["error"]}
                 continue
+            if labels:
+                r["labels_written"] = False
             if r["final_metrics"] is not None:
                 if plot:
                     r["figure"] = write_plot_packed(names[k], output_directory, params, r)
                 write_reports_packed(names[k], output_directory, r, hints[k])
+                if labels and r["labels"] is not None:
+                    r["labels_written"] = LB.write_labels(LB.labels_path(names[k], output_directory), r["labels"],
+                                                          overwrite=labels_overwrite)
             out[k] = r
     return out
 

@@ -489,6 +489,91 @@ class Metrics:
         return out
 
 
+_LABEL_ROWS = ("lb_pos", "lb_type", "lb_time", "lb_bpm", "pr_s1", "pr_s2", "pr_dt", "gr_id", "gr_first", "gr_last",
+               "gr_s1", "gr_pairs", "gr_dt", "gr_bpm")
+_LABEL_COUNT = {"lb": "n_labels", "pr": "n_pairs", "gr": "n_groups"}
+
+
+@dataclass
+class Labels:
+    """bpmx_labels_device's outputs for one batch (device tensors): per
+    recording the S1 / S2 label rows, the S1-S2 pairs, the groups that have
+    statistics, the three counts, the 4-double record (mean interval and BPM
+    over all pairs, labels of each type) and a status, in slices that start at
+    ``packed.pk_off[f]``."""
+    det: "object"
+    beats: Beats
+    gap_sec: float
+    lb_pos: "object"
+    lb_type: "object"
+    lb_time: "object"
+    lb_bpm: "object"
+    pr_s1: "object"
+    pr_s2: "object"
+    pr_dt: "object"
+    gr_id: "object"
+    gr_first: "object"
+    gr_last: "object"
+    gr_s1: "object"
+    gr_pairs: "object"
+    gr_dt: "object"
+    gr_bpm: "object"
+    n_labels: "object"
+    n_pairs: "object"
+    n_groups: "object"
+    record: "object"
+    status: "object"
+
+    def to_host(self) -> List[Optional[dict]]:
+        """Per recording the labels dict of ``labels.assemble`` (table, pairs,
+        groups, summary, gap_sec), or None where the stage made no labels
+        (BPMX_LABELS_NONE).  Two rounds of pinned copies like the other
+        results: offsets, counts, status and records first, then the used
+        prefix of each array.  Raises BpmxError (E_LIMIT) when the peak table
+        was too small."""
+        from . import labels as LB
+        torch = _torch()
+        det, pk = self.det, self.beats.packed
+        F = pk.n_files
+        with det.lock:
+            st = torch.cuda.current_stream(det.device)
+            small = {"pk_off": pk.pk_off, "l_n_labels": self.n_labels, "l_n_pairs": self.n_pairs,
+                     "l_n_groups": self.n_groups, "l_status": self.status, "l_record": self.record}
+            pin = {k: det.staging(k, t.numel(), t.dtype) for k, t in small.items()}
+            for k, h in pin.items():
+                h.copy_(small[k].reshape(-1), non_blocking=True)
+            st.synchronize()
+            meta = {k: h.numpy().copy() for k, h in pin.items()}
+            pko = meta["pk_off"]
+            tp = int(pko[F])
+            if tp > pk.cap_peaks or (meta["l_status"] == N.LABELS_OVERFLOW).any():
+                raise N.BpmxError(f"packed tables too small: {tp} peaks (capacity {pk.cap_peaks})", N.E_LIMIT)
+            # the used prefix of each kind of row: up to the last entry any file wrote
+            cnt = {c: meta["l_" + name] for c, name in _LABEL_COUNT.items()}
+            top = {c: int(max((int(pko[f]) + int(v[f]) for f in range(F) if v[f] > 0), default=0))
+                   for c, v in cnt.items()}
+            big = {"l_" + k: getattr(self, k) for k in _LABEL_ROWS}
+            pin = {k: det.staging(k, top[k[2:4]], t.dtype) for k, t in big.items() if top[k[2:4]] > 0}
+            for k, h in pin.items():
+                h.copy_(big[k][:top[k[2:4]]], non_blocking=True)
+            st.synchronize()
+            tab = {k[2:]: (pin[k].numpy().copy() if k in pin else np.zeros(0, _NP_OF[str(t.dtype)]))
+                   for k, t in big.items()}
+        rec = meta["l_record"].reshape(F, N.LABELS_RECORD)
+        out: List[Optional[dict]] = []
+        for f in range(F):
+            s, a = int(meta["l_status"][f]), int(pko[f])
+            if s == N.LABELS_NONE:
+                out.append(None)
+                continue
+            if s != N.LABELS_OK:
+                raise N.BpmxError(f"bpmx_labels_device: status {s} for recording {f}")
+            dev = {k: tab[k][a:a + int(cnt[k[:2]][f])] for k in _LABEL_ROWS}
+            dev["record"] = rec[f]
+            out.append(LB.assemble(dev, self.gap_sec))
+        return out
+
+
 class Detector:
     """One libbpmx context on one GPU.
 
@@ -1047,7 +1132,7 @@ class Detector:
         return out
 
     def set_options(self, options: int) -> None:
-        """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL; test/diagnostic)."""
+        """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL, N.OPT_LABELS_GLOBAL; test/diagnostic)."""
         with self.lock:
             N.check(self.L.bpmx_set_options(self.ctx, int(options)), "bpmx_set_options")
 
@@ -1104,6 +1189,44 @@ class Detector:
                     "bpmx_metrics_device")
         return out
 
+    def labels_device(self, beats: Beats, gap_sec: float = 5.0) -> Labels:
+        """bpmx_labels_device on the current stream, behind the
+        ``beats_device(trace=True)`` that filled `beats`: the labeler's output
+        (S1 / S2 label table, S1-S2 pairs, groups of marks with their
+        statistics, the mean interval) of every recording from its raw peaks,
+        tags, gap-fill labels, final beats and curve, on the GPU.  ``gap_sec``:
+        the pause that separates two groups.  Asynchronous; outputs are sized
+        by the peak table's capacity."""
+        torch = _torch()
+        if not hasattr(self.L, "bpmx_labels_device"):
+            raise N.BpmxError("libbpmx.so has no bpmx_labels_device; rebuild")
+        if beats.trace is None:
+            raise N.BpmxError("labels_device needs beats_device(trace=True): the gap-fill labels decide the types",
+                              N.E_ARG)
+        packed = beats.packed
+        F, cap, dev = packed.n_files, max(int(packed.cap_peaks), 1), self.device
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        rows = {k: e(cap, torch.float64 if k in ("lb_time", "lb_bpm", "pr_dt", "gr_dt", "gr_bpm") else torch.int32)
+                for k in _LABEL_ROWS}
+        out = Labels(det=self, beats=beats, gap_sec=float(gap_sec), n_labels=e(F, torch.int32),
+                     n_pairs=e(F, torch.int32), n_groups=e(F, torch.int32),
+                     record=e(F * N.LABELS_RECORD, torch.float64), status=e(F, torch.int32), **rows)
+        k = N.PackedOut()
+        k.cap_peaks, k.pk_off, k.pk_idx = packed.cap_peaks, packed.pk_off.data_ptr(), packed.pk_idx.data_ptr()
+        b = N.BeatsOut()
+        b.final_idx, b.n_final = beats.final_idx.data_ptr(), beats.n_final.data_ptr()
+        b.bpm_t, b.bpm, b.n_bpm = beats.bpm_t.data_ptr(), beats.bpm.data_ptr(), beats.n_bpm.data_ptr()
+        b.tags, b.status = beats.tags.data_ptr(), beats.status.data_ptr()
+        o = N.LabelsOut()
+        for name, _ in N.LabelsOut._fields_:
+            setattr(o, name, getattr(out, name).data_ptr())
+        lp = N.LabelParams(float(gap_sec))
+        with self.lock:
+            N.check(self.L.bpmx_labels_device(self.ctx, F, int(packed.sr), ctypes.byref(lp), ctypes.byref(k),
+                                              ctypes.byref(b), beats.trace.gap.data_ptr(), ctypes.byref(o),
+                                              self.stream_handle()), "bpmx_labels_device")
+        return out
+
     def run_host_metrics(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                          hint: Optional[float] = None, resolve_ties: bool = True,
                          longest_first: bool = True, assemble: bool = True) -> List[dict]:
@@ -1127,7 +1250,8 @@ class Detector:
 
     def run_host_reports(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                          hints: Optional[Sequence[Optional[float]]] = None, resolve_ties: bool = True,
-                         longest_first: bool = True, plot: bool = False) -> List[dict]:
+                         longest_first: bool = True, plot: bool = False, labels: bool = False,
+                         label_gap_sec: float = 5.0) -> List[dict]:
         """Everything the reference's report set needs, with no classifier on
         the host: upload, run, ``resolve_ties``, ``pack`` (with the floor at
         the troughs, and the int16 debug samples when
@@ -1140,7 +1264,10 @@ class Detector:
         ``reports.write_reports_packed`` takes.  With `plot`, each dict also
         carries ``env_plot``, ``floor_plot`` and ``plot_factor``
         (``pack_plot`` at ``params['plot_downsample_factor']``, default 5 as in
-        the reference), which ``plot.build_figure_packed`` takes.  Same lock,
+        the reference), which ``plot.build_figure_packed`` takes.  With
+        `labels`, each dict also carries ``labels`` (``labels_device`` at
+        `label_gap_sec`, ``Labels.to_host``: the labeler's table, pairs, groups
+        and summary, or None where there are none).  Same lock,
         stream and longest-first rules as ``run_host_packed``."""
         torch = _torch()
         recordings = list(recordings)
@@ -1161,7 +1288,12 @@ class Detector:
             if plot:
                 ps = self.pack_plot(res, plot_device_factor(params.get("plot_downsample_factor", 5)))
             b = self.beats_device(pk, params, hints=hh, trace=True)
-            got = self.metrics_device(b, params).to_host(explain=True)
+            met = self.metrics_device(b, params)
+            if labels:
+                lab = self.labels_device(b, label_gap_sec)
+            got = met.to_host(explain=True)
+            if labels:
+                labs = lab.to_host()
             tabs = pk.to_host()
             if plot:
                 series = ps.to_host()
@@ -1169,6 +1301,8 @@ class Detector:
         out: List[dict] = [None] * len(recordings)
         for k, i in enumerate(perm):
             out[i] = dict(tabs[k], **got[k])
+            if labels:
+                out[i]["labels"] = labs[k]
             if plot:
                 if tabs[k]["flags"] & N.F_TOO_SHORT:    # no outputs: empty series, not the buffers' old contents
                     series[k]["env_plot"], series[k]["floor_plot"] = np.zeros(0), np.zeros(0)

@@ -25,6 +25,9 @@
  *                                 plot_downsample_factor-th sample
  *   bpmx_metrics_device        <- bpm_analysis.py:1701-1722  _calculate_final_metrics on the beats and
  *                                 the curve (HRV table, summary, HRR, slopes, inclines and declines)
+ *   bpmx_labels_device         <- heartbeat_labeler.py  the labeler's output from the beat stages'
+ *                                 decisions: the S1 / S2 table of <base>_labels.csv (:530-546), the
+ *                                 S1-S2 pairs (:198-217), the groups and their statistics (:244-308)
  *   bpmx_synth / bpmx_synth_host   deterministic synthetic recordings (bench/tests)
  *
  * Plain C types only.  PCM and result arrays are DEVICE pointers (HBM); the
@@ -48,7 +51,7 @@ extern "C" {
 #endif
 
 /* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
- * BPMX_OPT_RECT_SEQ. */
+ * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
@@ -158,9 +161,11 @@ enum bpmx_option {
     BPMX_OPT_METRICS_GLOBAL = 32768, /* bpmx_metrics_device (set with bpmx_set_options): every recording's
                                         workspace in global memory, the curve and beats read where they lie
                                         (test/diagnostic) */
-    BPMX_OPT_RECT_SEQ = 65536        /* rectified mode: the general route (the pandas recursion, one lane per
+    BPMX_OPT_RECT_SEQ = 65536,       /* rectified mode: the general route (the pandas recursion, one lane per
                                         recording) for every recording, also where the exact-integer route
                                         applies (test/diagnostic) */
+    BPMX_OPT_LABELS_GLOBAL = 131072  /* bpmx_labels_device (set with bpmx_set_options): every recording's
+                                        workspace in global memory instead of LDS (test/diagnostic) */
 };
 
 /* bpmx_stats counters of the last run with BPMX_OPT_STATS */
@@ -519,8 +524,83 @@ int bpmx_metrics_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_m
                         int64_t epoch_us, const bpmx_packed *tables, const bpmx_beats_out *beats,
                         const bpmx_metrics_out *out, void *stream);
 
+/* The labeler's output on the device (bpmx_labels_device).
+ *
+ * heartbeat_labeler.py exists to produce <base>_labels.csv (a table of S1 and
+ * S2 marks: time, average BPM, type) and the S1-S2 interval analysis over it.
+ * There a person clicks every mark; here the marks are the beat stages' own
+ * decisions, read where bpmx_beats_device_ex left them:
+ *
+ *   S1: every final beat (final_idx).
+ *   S2: every raw peak that is not a final beat and whose final debug string
+ *       is an S2: the label of the highest gap-fill pass that touched it
+ *       (trace gap), else the main pass' tag.  Nothing else is labelled.
+ *
+ * A label is what the labeler appends for a click exactly on the peak
+ * (:530-546), x = idx / sr:  time = round(x, 3) (Python's round, the correctly
+ * rounded decimal), BPM = round(B[argmin |T - x|], 3) over the rows (T, B) of
+ * <base>_bpm_plot.csv (the curve rows whose BPM is not NaN, each value as
+ * float(f"{v:.3f}"); the first minimum wins).  Labels ascend in time.  Pairs
+ * are calculate_s1_s2_diffs' greedy walk (:198-217), groups
+ * detect_labeling_groups (:244-276) at gap_sec, their statistics
+ * calculate_group_statistics (:278-308): sums added left to right.  The
+ * arithmetic is csrc/bpmx_labels_core.h.
+ *
+ * A recording never has more labels than raw peaks, nor more pairs or groups,
+ * so every output slice starts at pk_off[f].  Label positions (pr_*, gr_first,
+ * gr_last) index the file's label rows; lb_pos is the raw peak's position in
+ * the file's slice of the peak table. */
+typedef struct {
+    double gap_sec;             /* detect_labeling_groups' gap_threshold; the labeler's group panel starts at 5 */
+} bpmx_label_params;
+
+enum bpmx_label_type { BPMX_LABEL_S1 = 1, BPMX_LABEL_S2 = 2 };
+
+enum bpmx_labels_status {       /* bpmx_labels_out.status */
+    BPMX_LABELS_OK = 0,
+    BPMX_LABELS_NONE = -20,     /* the beat stages did not finish with BPMX_HOST_OK, fewer than two final beats
+                                   (the reference writes no CSV), or no curve row that is not NaN: counts 0,
+                                   record NaN */
+    BPMX_LABELS_OVERFLOW = -21  /* the file's slice reaches past cap_peaks: nothing written but the status */
+};
+
+/* bpmx_labels_out.record: 4 doubles per file */
+enum bpmx_labels_record {
+    BPMX_LR_AVG_DT = 0,         /* mean S1-S2 interval over all pairs (calculate_avg_delta_t_in_range over the
+                                   whole table), NaN without pairs */
+    BPMX_LR_AVG_BPM = 1,        /* mean BPM of the pairs' S1 rows, NaN without pairs */
+    BPMX_LR_N_S1 = 2, BPMX_LR_N_S2 = 3,   /* labels of each type */
+    BPMX_LABELS_RECORD = 4
+};
+
+typedef struct {            /* device; per-file slices start at pk_off[f] */
+    int32_t *lb_pos, *lb_type;            /* [cap_peaks] label rows: raw-peak position, bpmx_label_type */
+    double *lb_time, *lb_bpm;             /* [cap_peaks] 'Time (s)', 'Average BPM'; n_labels[f] valid */
+    int32_t *pr_s1, *pr_s2;               /* [cap_peaks] pairs: the two label rows */
+    double *pr_dt;                        /* [cap_peaks] S2 time - S1 time, unrounded; n_pairs[f] valid */
+    int32_t *gr_id, *gr_first, *gr_last;  /* [cap_peaks] groups with statistics: group_id (may jump), first and
+                                             last S1 label row */
+    int32_t *gr_s1, *gr_pairs;            /* [cap_peaks] s1_count, pairs_count */
+    double *gr_dt, *gr_bpm;               /* [cap_peaks] avg_delta_t, avg_bpm; n_groups[f] valid */
+    int32_t *n_labels, *n_pairs, *n_groups;   /* [n_files] */
+    double *record;                       /* [n_files][BPMX_LABELS_RECORD] */
+    int32_t *status;                      /* [n_files] bpmx_labels_status */
+} bpmx_labels_out;
+
+/* The labels of n_files recordings from `beats` (the outputs of
+ * bpmx_beats_device_ex over `tables`: pk_off, pk_idx and cap_peaks are read
+ * from the tables; final_idx, n_final, bpm_t, bpm, n_bpm, tags and status from
+ * the beats) and `gap` (bpmx_trace_out.gap of the same launch, required),
+ * asynchronously on `stream`, ordered after the beat stages.  Never
+ * synchronises the host; scratch comes from ctx.  Every pointer of `out` is
+ * required.  One workgroup per recording; see csrc/k_labels.hip. */
+int bpmx_labels_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_label_params *params,
+                       const bpmx_packed *tables, const bpmx_beats_out *beats, const int32_t *gap,
+                       const bpmx_labels_out *out, void *stream);
+
 /* bpmx_option bits for the entry points that take no bpmx_params
- * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL); they hold until set again. */
+ * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL);
+ * they hold until set again. */
 int bpmx_set_options(bpmx_ctx *ctx, int32_t options);
 
 /* Synthetic int16 recordings straight into HBM: file f gets seed seed0+f,
