@@ -40,6 +40,7 @@ OPT_BEATS_GLOBAL = 16384           # bpmx_beats_device, through bpmx_set_options
 OPT_METRICS_GLOBAL = 32768         # bpmx_metrics_device, through bpmx_set_options (test/diagnostic)
 OPT_RECT_SEQ = 65536               # rectified mode: the pandas recursion for every recording (test/diagnostic)
 OPT_LABELS_GLOBAL = 131072          # bpmx_labels_device, through bpmx_set_options (test/diagnostic)
+OPT_SCORE_GLOBAL = 262144           # bpmx_score_device, through bpmx_set_options (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS
@@ -52,6 +53,11 @@ MR_HRR_PEAK, MR_HRR_RECOVERY_BPM, MR_HRR_VALUE, MR_RECOVERY, MR_EXERTION, METRIC
 LABELS_OK, LABELS_NONE, LABELS_OVERFLOW = 0, -20, -21
 LABEL_S1, LABEL_S2 = 1, 2
 LR_AVG_DT, LR_AVG_BPM, LR_N_S1, LR_N_S2, LABELS_RECORD = 0, 1, 2, 3, 4
+# bpmx_score_out.status (0, the bit, or a negative code), the mark kinds and .record (20 int64 per file)
+SCORE_OK, SCORE_NO_LABELS, SCORE_NONE, SCORE_OVERFLOW = 0, 1, -22, -23
+SCORE_OUTSIDE, SCORE_TP, SCORE_SWAP, SCORE_FP, SCORE_FN = 0, 1, 2, 3, 3
+SR_N_REF, SR_N_DET, SR_TP, SR_SWAP, SR_FP, SR_FN, SR_SUM_ERR, SR_SUM_ABS, SR_MAX_ABS = 0, 1, 2, 3, 4, 5, 6, 7, 8
+SR_PER_TYPE, SR_N_OUTSIDE, SR_N_SPANS, SCORE_RECORD = 9, 18, 19, 20
 # bpmx_trace_out.record (bpmx_trace_field: 18 doubles per raw peak), .code (bpmx_trace_code) and .gap
 TR_BLEND, TR_BASE_CONF, TR_STAB_FACTOR, TR_STAB_RATIO, TR_ADJ_AMOUNT, TR_ADJ_RATIO, TR_ADJ_RMAX = 0, 1, 2, 3, 4, 5, 6
 TR_IV_AMOUNT, TR_IV_GAP, TR_IV_CAP, TR_FINAL = 7, 8, 9, 10
@@ -64,7 +70,7 @@ EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
            "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
            "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot",
-           "bpmx_labels_device"]
+           "bpmx_labels_device", "bpmx_score_device"]
 
 
 class Params(ctypes.Structure):
@@ -155,6 +161,23 @@ class LabelsOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in (
         "lb_pos", "lb_type", "lb_time", "lb_bpm", "pr_s1", "pr_s2", "pr_dt", "gr_id", "gr_first", "gr_last",
         "gr_s1", "gr_pairs", "gr_dt", "gr_bpm", "n_labels", "n_pairs", "n_groups", "record", "status")]
+
+
+class ScoreParams(ctypes.Structure):
+    """bpmx_score_params: the matching tolerance and the pause that ends a labelled span, milliseconds."""
+    _fields_ = [("tol_ms", ctypes.c_int32), ("gap_ms", ctypes.c_int32)]
+
+
+class RefMarks(ctypes.Structure):
+    """bpmx_ref_marks: the corrected marks as a ragged device table (labels.marks_from_table)."""
+    _fields_ = [("cap_ref", ctypes.c_int64), ("rf_off", ctypes.c_void_p), ("rf_ms", ctypes.c_void_p),
+                ("rf_type", ctypes.c_void_p)]
+
+
+class ScoreOut(ctypes.Structure):
+    """bpmx_score_out: the device arrays bpmx_score_device fills (the four
+    row arrays in slices at pk_off[f] / rf_off[f], all of them or none)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("sc_kind", "sc_ref", "rf_kind", "rf_det", "record", "status")]
 
 
 class BpmxError(RuntimeError):
@@ -251,6 +274,11 @@ def load() -> ctypes.CDLL:
         L.bpmx_labels_device.argtypes = [P, I32, I32, ctypes.POINTER(LabelParams), ctypes.POINTER(PackedOut),
                                          ctypes.POINTER(BeatsOut), P, ctypes.POINTER(LabelsOut), P]
         L.bpmx_labels_device.restype = ctypes.c_int
+    if hasattr(L, "bpmx_score_device"):
+        L.bpmx_score_device.argtypes = [P, I32, ctypes.POINTER(ScoreParams), ctypes.POINTER(PackedOut),
+                                        ctypes.POINTER(LabelsOut), ctypes.POINTER(RefMarks),
+                                        ctypes.POINTER(ScoreOut), P]
+        L.bpmx_score_device.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

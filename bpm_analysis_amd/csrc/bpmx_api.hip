@@ -2,7 +2,8 @@
  * bpmx_api.hip — host side of the C ABI (include/bpmx.h): context, scratch,
  * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
  * bpmx_pack_trough_floor, bpmx_pack_plot, bpmx_beats_device,
- * bpmx_beats_device_ex, bpmx_metrics_device and bpmx_labels_device.
+ * bpmx_beats_device_ex, bpmx_metrics_device, bpmx_labels_device and
+ * bpmx_score_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -118,6 +119,24 @@ int labels_stage(bpmx_ctx *ctx, const LabelsPlan &L, int32_t n_files, int32_t sr
         if (rc != BPMX_OK) return rc;
     }
     LAUNCH(ctx, s, "k_labels", k_labels, dim3(L.grid), dim3(LABELS_T), L.lds, s, a);
+    return BPMX_OK;
+}
+
+/* the scores behind the labels: one launch sized by the plan */
+int score_stage(bpmx_ctx *ctx, const ScorePlan &S, int32_t n_files, const bpmx_score_params &P, const bpmx_packed &t,
+                const bpmx_labels_out &l, const bpmx_ref_marks &r, const bpmx_score_out &o, hipStream_t s) {
+    int rc = BPMX_OK;
+    ScoreArgs a{};
+    a.n_files = n_files; a.cap = t.cap_peaks; a.cap_ref = r.cap_ref; a.lds = S.lds; a.fixed = S.fixed;
+    a.pk_off = t.pk_off;
+    a.lb_time = l.lb_time; a.lb_type = l.lb_type; a.n_labels = l.n_labels; a.l_status = l.status;
+    a.rf_off = r.rf_off; a.rf_ms = r.rf_ms; a.rf_type = r.rf_type;
+    a.P = P; a.O = o;
+    if (S.any_global) {
+        a.gws = (unsigned char *)ctx->buf("score_ws", S.gws, &rc);
+        if (rc != BPMX_OK) return rc;
+    }
+    LAUNCH(ctx, s, "k_score", k_score, dim3(S.grid), dim3(SCORE_T), S.lds, s, a);
     return BPMX_OK;
 }
 
@@ -710,6 +729,35 @@ int bpmx_labels_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_la
     HIP_TRY(hipSetDevice(ctx->device));
     return labels_stage(ctx, labels_plan(n_files, tables->cap_peaks, ctx->options), n_files, sr, *params, *tables,
                         *beats, gap, *out, (hipStream_t)stream);
+}
+
+int bpmx_score_device(bpmx_ctx *ctx, int32_t n_files, const bpmx_score_params *params, const bpmx_packed *tables,
+                      const bpmx_labels_out *labels, const bpmx_ref_marks *ref, const bpmx_score_out *out,
+                      void *stream) {
+    if (!ctx || !params || !tables || !labels || !ref || !out)
+        return fail(BPMX_E_ARG, "bpmx_score_device: NULL argument");
+    if (n_files < 0) return fail(BPMX_E_ARG, "bpmx_score_device: bad n_files");
+    if (params->tol_ms < 0) return fail(BPMX_E_ARG, "bpmx_score_device: needs tol_ms >= 0");
+    if ((int64_t)params->gap_ms <= 2 * (int64_t)params->tol_ms)
+        return fail(BPMX_E_ARG, "bpmx_score_device: needs gap_ms > 2 * tol_ms (the labelled spans must stay apart)");
+    if (n_files == 0) return BPMX_OK;
+    if (!tables->pk_off || tables->cap_peaks < 0 || tables->cap_peaks >= (int64_t)INT_MAX)
+        return fail(BPMX_E_ARG, "bpmx_score_device: needs pk_off and 0 <= cap_peaks < 2^31");
+    if (!labels->lb_time || !labels->lb_type || !labels->n_labels || !labels->status)
+        return fail(BPMX_E_ARG, "bpmx_score_device: the labels' lb_time, lb_type, n_labels and status are required");
+    if (!ref->rf_off || ref->cap_ref < 0 || ref->cap_ref >= (int64_t)INT_MAX ||
+        (ref->cap_ref > 0 && (!ref->rf_ms || !ref->rf_type)))
+        return fail(BPMX_E_ARG, "bpmx_score_device: needs rf_off, 0 <= cap_ref < 2^31 and, with cap_ref > 0, rf_ms "
+                                "and rf_type");
+    const int rows = (out->sc_kind != nullptr) + (out->sc_ref != nullptr) + (out->rf_kind != nullptr) +
+                     (out->rf_det != nullptr);
+    if (rows != 0 && rows != 4)
+        return fail(BPMX_E_ARG, "bpmx_score_device: sc_kind, sc_ref, rf_kind and rf_det are given together or not "
+                                "at all");
+    if (!out->record || !out->status) return fail(BPMX_E_ARG, "bpmx_score_device: record and status are required");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return score_stage(ctx, score_plan(n_files, tables->cap_peaks, ref->cap_ref, ctx->options), n_files, *params,
+                       *tables, *labels, *ref, *out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -600,6 +600,25 @@ struct LabelsArgs {
 };
 __global__ void k_labels(LabelsArgs A);
 
+/* bpmx_score_device (k_score.hip): one workgroup of SCORE_T threads per recording */
+enum { SCORE_T = 256 };
+struct ScoreArgs {
+    int32_t n_files;
+    int64_t cap, cap_ref;       /* capacities of the label rows and of the reference marks, entries */
+    size_t lds;                 /* a recording whose workspace is at most this many bytes works in LDS (0: none) */
+    size_t fixed;               /* score_ws_fixed(SCORE_T): a global slice starts at
+                                   f * fixed + SC_STRIDE * (pk_off[f] + rf_off[f]) */
+    const int64_t *pk_off;      /* [F+1] */
+    const double *lb_time;      /* k_labels' outputs */
+    const int32_t *lb_type, *n_labels, *l_status;
+    const int64_t *rf_off;      /* [F+1] */
+    const int32_t *rf_ms, *rf_type;
+    unsigned char *gws;         /* workspaces of the recordings beyond lds (bpmx_plan.h score_plan) */
+    bpmx_score_params P;
+    bpmx_score_out O;
+};
+__global__ void k_score(ScoreArgs A);
+
 /* Rectified-mode envelope (k_rect.hip): the centred rolling mean of |x| at the
  * native rate.  Integer PCM of one or two channels takes the exact-integer
  * route (window sums from int64 prefix sums, one division); everything else

@@ -14,6 +14,7 @@
 #include "bpmx_beats_core.h"
 #include "bpmx_metrics_core.h"
 #include "bpmx_labels_core.h"
+#include "bpmx_score_core.h"
 #include "bpmx_rect_core.h"
 #include "bpmx_kernels.h"
 
@@ -341,6 +342,38 @@ inline LabelsPlan labels_plan(int F, int64_t cap_peaks, int32_t options, size_t 
     L.fixed = labels_ws_fixed(LABELS_T);
     L.gws = L.any_global ? (size_t)F * L.fixed + (size_t)cap_peaks * LB_STRIDE : 0;
     return L;
+}
+
+/* bpmx_score_device: one workgroup of SCORE_T threads per recording
+ * (k_score).  A recording's workspace (bpmx_score_core.h: 17 bytes per label
+ * row, 21 per reference mark) lives in LDS when it fits SCORE_LDS_BUDGET:
+ * 32 KB, so five workgroups share a CU's 160 KB, and the 605 labels a 60 s
+ * recording can have with as many reference marks are inside it.  Longer
+ * tables take a slice of one global buffer at
+ * f * fixed + SC_STRIDE * (pk_off[f] + rf_off[f]).  Sized from the two
+ * capacities and the file count alone. */
+constexpr size_t SCORE_LDS_BUDGET = 32 * 1024;
+
+struct ScorePlan {
+    unsigned grid;              /* workgroups: one per recording */
+    size_t lds;                 /* dynamic LDS bytes per workgroup: the largest workspace of an LDS-path recording
+                                   (0: every recording goes global) */
+    bool any_global;
+    size_t fixed;               /* score_ws_fixed(SCORE_T) */
+    size_t gws;                 /* bytes of the global workspace buffer (0: none) */
+};
+
+inline ScorePlan score_plan(int F, int64_t cap_peaks, int64_t cap_ref, int32_t options,
+                            size_t budget = SCORE_LDS_BUDGET) {
+    ScorePlan S{};
+    S.grid = (unsigned)F;
+    const bool forced = (options & BPMX_OPT_SCORE_GLOBAL) != 0;
+    const size_t all = score_ws_bytes(cap_peaks, cap_ref, SCORE_T);     /* the largest workspace a recording can need */
+    S.lds = forced || budget < score_ws_bytes(0, 0, SCORE_T) ? 0 : std::min(all, budget);
+    S.any_global = all > S.lds;
+    S.fixed = score_ws_fixed(SCORE_T);
+    S.gws = S.any_global ? (size_t)F * S.fixed + (size_t)(cap_peaks + cap_ref) * SC_STRIDE : 0;
+    return S;
 }
 
 }  // namespace bpmx

@@ -432,6 +432,88 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     return out
 
 
+def score_wav_files(file_paths: Sequence[str], params_list: Sequence[Dict], label_paths: Sequence[str] = None,
+                    mode: str = None, device: int = 0, tol_sec: float = 0.05, label_gap_sec: float = 5.0,
+                    start_bpm_hints: Sequence = None) -> List[dict]:
+    """How well each setting of `params_list` reproduces the corrected labels
+    of an archive: every file is analysed with every setting on the device
+    (``Detector.score_sweep``: the envelope once per file, then detection,
+    beat stages, labels and the scoring per setting) and only the integer
+    records come back.  With ``mode="rectified"`` the files are the
+    ``_filtered_debug.wav`` files of an earlier run, so the original audio is
+    not needed.
+
+    ``label_paths``: one corrected ``_labels.csv`` per file (default:
+    ``labels.labels_path`` beside the WAV, which is where
+    ``analyze_wav_files_to_reports(labels=True)`` writes it and the labeler
+    saves it).  A file that cannot be read, or whose label file is missing,
+    unreadable or without an S1 / S2 mark, is a per-file ``error`` entry; the
+    others still score.  Files are grouped by (rate, format, channels) as
+    ``analyze_wav_files`` groups them.
+
+    Returns one dict per setting, in order: ``params``, ``files`` (per path
+    ``labels.score_summary``'s dict with ``record`` and ``status``, or
+    ``error``) and ``total`` (the summary of the files' records added,
+    ``labels.score_total``) with its ``record`` and ``n_files``."""
+    from . import labels as LB
+    params_list = [dict(p) for p in params_list]
+    if mode is None:
+        mode = params_list[0].get("bpmx_mode", "reference") if params_list else "reference"
+    n = len(file_paths)
+    hints = [None] * n if start_bpm_hints is None else list(start_bpm_hints)
+    if label_paths is None:
+        label_paths = [LB.labels_path(p, os.path.dirname(p)) for p in file_paths]
+    if len(hints) != n or len(label_paths) != n:
+        raise ValueError("start_bpm_hints and label_paths need one entry per file")
+    LB.score_ms(tol_sec, label_gap_sec)
+    errors: Dict[int, Exception] = {}
+    groups: Dict[tuple, List[int]] = {}
+    audio, refs = [None] * n, [None] * n
+    for k, path in enumerate(file_paths):
+        try:
+            if not os.path.exists(label_paths[k]):
+                raise FileNotFoundError(f"no label file {label_paths[k]}")
+            refs[k] = LB.marks_from_table(LB.read_labels(label_paths[k]))
+            if len(refs[k]["ms"]) == 0:
+                raise ValueError(f"{label_paths[k]} holds no S1 or S2 mark")
+            fs, a = _read_wav(path)
+        except Exception as exc:                      # per file, as in the GUI loop
+            errors[k] = exc
+            continue
+        audio[k] = a
+        groups.setdefault((fs, a.dtype.str, 1 if a.ndim == 1 else a.shape[1]), []).append(k)
+    det = default_detector(device)
+    records = np.zeros((len(params_list), n, N.SCORE_RECORD), np.int64)
+    status = np.zeros((len(params_list), n), np.int32)
+    for (fs, _, _), idx in groups.items():
+        try:
+            rec, st = det.score_sweep([audio[k] for k in idx], fs, params_list, [refs[k] for k in idx], mode=mode,
+                                      hints=[hints[k] for k in idx], tol_sec=tol_sec, gap_sec=label_gap_sec)
+        except (ValueError, N.BpmxError) as exc:
+            if isinstance(exc, N.BpmxError) and not exc.per_file:
+                raise                                 # HIP / device failure: not a per-file error
+            if len({p["downsample_factor"] for p in params_list}) > 1:
+                raise                                 # the caller's grid, not a file
+            for k in idx:
+                errors[k] = exc
+            continue
+        records[:, idx], status[:, idx] = rec, st
+    good = [k for k in range(n) if k not in errors]
+    out = []
+    for p, params in enumerate(params_list):
+        files = []
+        for k in range(n):
+            if k in errors:
+                files.append({"error": errors[k]})
+            else:
+                files.append(dict(LB.score_summary(records[p, k]), record=records[p, k].copy(),
+                                  status=int(status[p, k])))
+        tot = LB.score_total(records[p, good])
+        out.append({"params": params, "files": files,
+                    "total": dict(LB.score_summary(tot), record=tot, n_files=len(good))})
+    return out
+
+
 def patch_reference(module) -> None:
     """Rebind an imported reference ``bpm_analysis`` module's hot path to the GPU.
 

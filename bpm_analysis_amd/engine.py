@@ -574,6 +574,96 @@ class Labels:
         return out
 
 
+@dataclass
+class Marks:
+    """A person's corrected marks of one batch on the device
+    (``Detector.upload_marks``): the ragged table bpmx_ref_marks takes, with
+    the host's copy (``labels.marks_from_table`` per recording)."""
+    det: "object"
+    host: List[dict]
+    off: np.ndarray              # [F + 1] int64
+    rf_off: "object"
+    rf_ms: "object"
+    rf_type: "object"
+
+    @property
+    def n_files(self) -> int:
+        return len(self.host)
+
+    @property
+    def cap_ref(self) -> int:
+        return int(self.off[-1])
+
+
+@dataclass
+class Scores:
+    """bpmx_score_device's outputs for one batch (device tensors): per
+    recording the 20-int64 record and a status and, with rows, the kind and
+    partner of every label row (slices at ``pk_off[f]``) and of every
+    reference mark (slices at ``marks.off[f]``)."""
+    det: "object"
+    labels: Labels
+    marks: Marks
+    tol_ms: int
+    gap_ms: int
+    record: "object"
+    status: "object"
+    sc_kind: "object" = None
+    sc_ref: "object" = None
+    rf_kind: "object" = None
+    rf_det: "object" = None
+
+    def download(self):
+        """(record [F, 20] int64, status [F] int32) on the host: the one
+        small copy a settings sweep needs.  Raises BpmxError (E_LIMIT) where a
+        table was too small."""
+        torch = _torch()
+        det, F = self.det, self.marks.n_files
+        with det.lock:
+            st = torch.cuda.current_stream(det.device)
+            hr = det.staging("s_record", F * N.SCORE_RECORD, self.record.dtype)
+            hs = det.staging("s_status", F, self.status.dtype)
+            hr[:F * N.SCORE_RECORD].copy_(self.record.reshape(-1), non_blocking=True)
+            hs[:F].copy_(self.status, non_blocking=True)
+            st.synchronize()
+            rec = hr[:F * N.SCORE_RECORD].numpy().copy().reshape(F, N.SCORE_RECORD)
+            status = hs[:F].numpy().copy()
+        if (status == N.SCORE_OVERFLOW).any():
+            raise N.BpmxError("bpmx_score_device: a label or reference table was too small", N.E_LIMIT)
+        return rec, status
+
+    def to_host(self) -> List[dict]:
+        """Per recording the dict of ``labels.score``: ``record``, ``status``,
+        ``marks`` and, with rows, ``sc_kind``, ``sc_ref``, ``rf_kind``,
+        ``rf_det`` (empty where the status is BPMX_SCORE_NONE)."""
+        torch = _torch()
+        rec, status = self.download()
+        F = self.marks.n_files
+        rows = None
+        if self.sc_kind is not None:
+            det, pk = self.det, self.labels.beats.packed
+            with det.lock:
+                t = {"pk_off": pk.pk_off, "n_labels": self.labels.n_labels, "l_status": self.labels.status,
+                     "sc_kind": self.sc_kind, "sc_ref": self.sc_ref, "rf_kind": self.rf_kind, "rf_det": self.rf_det}
+                rows = {k: v.cpu().numpy() for k, v in t.items()}     # .cpu() waits for the current stream
+                torch.cuda.current_stream(det.device).synchronize()
+        out = []
+        e32 = np.zeros(0, np.int32)
+        for f in range(F):
+            r = {"record": rec[f], "status": int(status[f]), "marks": self.marks.host[f], "tol_ms": self.tol_ms,
+                 "gap_ms": self.gap_ms}
+            if rows is not None:
+                if status[f] < 0:
+                    r.update(sc_kind=e32, sc_ref=e32, rf_kind=e32, rf_det=e32)
+                else:
+                    a, ra, rz = int(rows["pk_off"][f]), int(self.marks.off[f]), int(self.marks.off[f + 1])
+                    n = int(rows["n_labels"][f]) if rows["l_status"][f] == N.LABELS_OK else 0
+                    r.update(sc_kind=rows["sc_kind"][a:a + n], sc_ref=rows["sc_ref"][a:a + n],
+                             rf_kind=rows["rf_kind"][ra:rz], rf_det=rows["rf_det"][ra:rz])
+            out.append(r)
+        return out
+
+
 class Detector:
     """One libbpmx context on one GPU.
 
@@ -1132,7 +1222,8 @@ class Detector:
         return out
 
     def set_options(self, options: int) -> None:
-        """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL, N.OPT_LABELS_GLOBAL; test/diagnostic)."""
+        """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL, N.OPT_LABELS_GLOBAL,
+        N.OPT_SCORE_GLOBAL; test/diagnostic)."""
         with self.lock:
             N.check(self.L.bpmx_set_options(self.ctx, int(options)), "bpmx_set_options")
 
@@ -1226,6 +1317,127 @@ class Detector:
                                               ctypes.byref(b), beats.trace.gap.data_ptr(), ctypes.byref(o),
                                               self.stream_handle()), "bpmx_labels_device")
         return out
+
+    def upload_marks(self, tables: Sequence[Optional[dict]]) -> Marks:
+        """A person's corrected marks, one label table per recording
+        (``labels.read_labels``; None or an empty table: no marks), prepared by
+        ``labels.marks_from_table`` and uploaded as the ragged table
+        bpmx_score_device takes."""
+        from . import labels as LB
+        torch = _torch()
+        host = [t if t is not None and "ms" in t else LB.marks_from_table(t) for t in tables]
+        off = np.zeros(len(host) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m["ms"]) for m in host])
+        cat = lambda k: np.concatenate([m[k] for m in host] + [np.zeros(1, np.int32)]).astype(np.int32)  # noqa: E731
+        up = lambda a: torch.from_numpy(a).to(self.device)  # noqa: E731
+        return Marks(det=self, host=host, off=off, rf_off=up(off), rf_ms=up(cat("ms")), rf_type=up(cat("type")))
+
+    def score_device(self, labels: Labels, marks: Marks, tol_sec: float = 0.05, gap_sec: float = 5.0,
+                     rows: bool = True) -> Scores:
+        """bpmx_score_device on the current stream, behind the
+        ``labels_device`` that filled `labels`: every recording's label rows
+        scored against its corrected marks (``upload_marks``): per type TP,
+        SWAP, FP, FN and the timing errors of the TP, in integer milliseconds
+        (``labels.score`` is the same on the host).  ``tol_sec``: two marks
+        this close are the same beat (the default ``min_peak_distance_sec``);
+        ``gap_sec``: a pause this long between corrected marks ends a labelled
+        span, outside which a detection is not a mistake.  ``rows=False``:
+        record and status only.  Asynchronous."""
+        from . import labels as LB
+        torch = _torch()
+        if not hasattr(self.L, "bpmx_score_device"):
+            raise N.BpmxError("libbpmx.so has no bpmx_score_device; rebuild")
+        tol, gap = LB.score_ms(tol_sec, gap_sec)
+        packed = labels.beats.packed
+        F, cap, dev = packed.n_files, max(int(packed.cap_peaks), 1), self.device
+        if marks.n_files != F:
+            raise N.BpmxError("score_device: marks needs one table per recording", N.E_ARG)
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        out = Scores(det=self, labels=labels, marks=marks, tol_ms=tol, gap_ms=gap,
+                     record=e(F * N.SCORE_RECORD, torch.int64), status=e(F, torch.int32))
+        if rows:
+            out.sc_kind, out.sc_ref = e(cap, torch.int32), e(cap, torch.int32)
+            out.rf_kind, out.rf_det = e(max(marks.cap_ref, 1), torch.int32), e(max(marks.cap_ref, 1), torch.int32)
+        k = N.PackedOut()
+        k.cap_peaks, k.pk_off = packed.cap_peaks, packed.pk_off.data_ptr()
+        lo = N.LabelsOut()
+        lo.lb_time, lo.lb_type = labels.lb_time.data_ptr(), labels.lb_type.data_ptr()
+        lo.n_labels, lo.status = labels.n_labels.data_ptr(), labels.status.data_ptr()
+        r = N.RefMarks(marks.cap_ref, marks.rf_off.data_ptr(), marks.rf_ms.data_ptr(), marks.rf_type.data_ptr())
+        o = N.ScoreOut()
+        for name, _ in N.ScoreOut._fields_:
+            t = getattr(out, name)
+            setattr(o, name, None if t is None else t.data_ptr())
+        sp = N.ScoreParams(tol, gap)
+        with self.lock:
+            N.check(self.L.bpmx_score_device(self.ctx, F, ctypes.byref(sp), ctypes.byref(k), ctypes.byref(lo),
+                                             ctypes.byref(r), ctypes.byref(o), self.stream_handle()),
+                    "bpmx_score_device")
+        return out
+
+    def score_sweep(self, recordings: List[np.ndarray], fs: int, params_list: Sequence[dict],
+                    ref_tables: Sequence[Optional[dict]], mode: str = "reference",
+                    hints: Optional[Sequence[Optional[float]]] = None, tol_sec: float = 0.05, gap_sec: float = 5.0,
+                    resolve_ties: bool = True):
+        """How well each setting of `params_list` reproduces a person's
+        corrected marks (`ref_tables`: one label table per recording) on one
+        batch: PCM is uploaded and the envelope stage run once; then, per
+        setting, FLOOR | PEAKS on that envelope, ``resolve_ties``, ``pack``,
+        ``beats_device(trace=True)``, ``labels_device`` and
+        ``score_device(rows=False)``.  One download at the end returns
+        ``(record [P, F, 20] int64, status [P, F] int32)`` in the caller's
+        order of recordings.  The settings must agree in ``downsample_factor``,
+        the only key the envelope stage reads (ValueError otherwise, before
+        anything runs).  Same lock, stream and longest-first rules as
+        ``run_host_reports``."""
+        from . import labels as LB
+        torch = _torch()
+        recordings, params_list = list(recordings), [dict(p) for p in params_list]
+        nF, nP = len(recordings), len(params_list)
+        if len({p["downsample_factor"] for p in params_list}) > 1:
+            raise ValueError("score_sweep: the settings differ in downsample_factor, which the shared envelope "
+                             "is made with; sweep each value on its own")
+        if len(ref_tables) != nF:
+            raise ValueError("score_sweep: ref_tables needs one entry per recording")
+        hints = [None] * nF if hints is None else list(hints)
+        if len(hints) != nF:
+            raise ValueError("score_sweep: hints needs one entry per recording")
+        LB.score_ms(tol_sec, gap_sec)
+        if nF == 0 or nP == 0:
+            return np.zeros((nP, nF, N.SCORE_RECORD), np.int64), np.zeros((nP, nF), np.int32)
+        designs = [mode_design(fs, p, mode) for p in params_list]
+        for d in designs:
+            if d.distance < 1:
+                raise ValueError("`distance` must be greater or equal to 1")
+        perm = list(range(nF))
+        if len({r.shape[0] for r in recordings}) > 1:
+            from .shard import longest_first as _lf
+            perm = list(_lf([r.shape[0] for r in recordings]))
+        recs, hh = [recordings[i] for i in perm], [hints[i] for i in perm]
+        det_st = N.STAGE_FLOOR | N.STAGE_PEAKS
+        with self.lock, torch.cuda.stream(self.host_stream()):
+            marks = self.upload_marks([ref_tables[i] for i in perm])
+            res, _ = self._batch_on_device(recs, fs, params_list[0], mode, N.STAGE_ENVELOPE, False, False)
+            ch = 1 if recs[0].ndim == 1 else recs[0].shape[1]
+            got = []
+            for p, d in zip(params_list, designs):
+                self.run(None, res.frame_offsets, fs, p, mode=mode, stages=det_st, channels=ch, out=res, d=d)
+                if resolve_ties:
+                    self.resolve_ties(res, p, det_st)
+                b = self.beats_device(self.pack(res, d.distance), p, hints=hh, trace=True)
+                got.append(self.score_device(self.labels_device(b, gap_sec), marks, tol_sec, gap_sec, rows=False))
+            rec = torch.stack([s.record for s in got]).reshape(-1)
+            st = torch.stack([s.status for s in got]).reshape(-1)
+            hr, hs = self.staging("sw_record", rec.numel(), rec.dtype), self.staging("sw_status", st.numel(), st.dtype)
+            hr.copy_(rec, non_blocking=True)
+            hs.copy_(st, non_blocking=True)
+            self.host_stream().synchronize()
+            record = hr.numpy().copy().reshape(nP, nF, N.SCORE_RECORD)
+            status = hs.numpy().copy().reshape(nP, nF)
+        if (status == N.SCORE_OVERFLOW).any():
+            raise N.BpmxError("bpmx_score_device: a label or reference table was too small", N.E_LIMIT)
+        inv = np.argsort(np.asarray(perm))
+        return record[:, inv], status[:, inv]
 
     def run_host_metrics(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                          hint: Optional[float] = None, resolve_ties: bool = True,

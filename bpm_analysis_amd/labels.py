@@ -39,6 +39,10 @@ A result ("labels") is a dict:
 * ``summary``: ``n_labels``, ``n_s1``, ``n_s2``, ``n_pairs``, ``avg_delta_t``,
   ``avg_bpm`` (None without pairs)
 * ``gap_sec``: the group threshold
+
+The last part scores such a table against a person's corrected label file
+(``marks_from_table``, ``score``, ``score_summary``, ``score_csv_text``): the
+definition of ``Detector.score_device`` (bpmx_score_device) in plain Python.
 """
 from __future__ import annotations
 
@@ -361,3 +365,192 @@ def read_labels(path: str) -> Dict:
         return empty_table()
     with open(path, "r", encoding="utf-8") as f:
         return parse_labels(f.read())
+
+
+# ---------------------------------------------------------------- scoring against corrected labels
+# There is no reference implementation of scoring: include/bpmx.h (bpmx_score_device) is the definition,
+# csrc/bpmx_score_core.h states it for host and device, and this is the same in plain Python.
+SCORE_OK, SCORE_NO_LABELS, SCORE_NONE, SCORE_OVERFLOW = 0, 1, -22, -23       # bpmx_score_status
+KIND_OUTSIDE, KIND_TP, KIND_SWAP, KIND_FP, KIND_FN = 0, 1, 2, 3, 3            # bpmx_score_kind
+KIND_NAME = {KIND_OUTSIDE: "OUTSIDE", KIND_TP: "TP", KIND_SWAP: "SWAP", KIND_FP: "FP"}
+# bpmx_score_record: nine fields per type (S1, then S2), then two for the file
+SR_N_REF, SR_N_DET, SR_TP, SR_SWAP, SR_FP, SR_FN, SR_SUM_ERR, SR_SUM_ABS, SR_MAX_ABS = range(9)
+SR_PER_TYPE, SR_N_OUTSIDE, SR_N_SPANS, SCORE_RECORD = 9, 18, 19, 20
+SCORE_COLUMNS = ("Time (s)", "Peak Type", "Kind", "Partner Time (s)")
+_I32 = (-2 ** 31, 2 ** 31 - 1)
+
+
+def _ms(times) -> np.ndarray:
+    """Integer milliseconds: one multiplication, round to nearest even, saturated to int32."""
+    q = np.rint(np.asarray(times, dtype=np.float64) * 1000.0)
+    q = np.where(np.isnan(q), _I32[0], q)
+    return np.clip(q, _I32[0], _I32[1]).astype(np.int64).astype(np.int32)
+
+
+def score_ms(tol_sec: float, gap_sec: float):
+    """(tol_ms, gap_ms) of the two thresholds in seconds; ValueError unless
+    tol_ms >= 0 and gap_ms > 2 * tol_ms (the labelled spans must stay apart)."""
+    tol, gap = int(round(float(tol_sec) * 1000)), int(round(float(gap_sec) * 1000))
+    if tol < 0 or gap <= 2 * tol or gap > _I32[1]:
+        raise ValueError(f"score: needs tol_ms >= 0 and gap_ms > 2 * tol_ms (got {tol}, {gap})")
+    return tol, gap
+
+
+def marks_from_table(table: Optional[Dict]) -> Dict:
+    """The reference marks of a corrected label table (``read_labels``), as
+    they are uploaded: rows whose type is neither S1 nor S2 or whose time is
+    NaN dropped (``dropped`` counts them), ``ms = int(np.rint(time * 1000.0))``,
+    sorted stably by ms.  ``row`` is each mark's row in `table`."""
+    if table is None:
+        table = empty_table()
+    typ = np.asarray(table["type"]).astype(np.int64)
+    t = np.asarray(table["time"], dtype=np.float64)
+    keep = np.flatnonzero(((typ == S1) | (typ == S2)) & ~np.isnan(t))
+    ms = _ms(t[keep])
+    order = np.argsort(ms, kind="stable")
+    return {"ms": ms[order], "type": typ[keep][order].astype(np.int32), "time": t[keep][order],
+            "row": keep[order].astype(np.int64), "dropped": int(len(typ) - len(keep))}
+
+
+def _walk(D: List[tuple], R: List[tuple], tol: int) -> List[tuple]:
+    """The walk over two ascending lists of (ms, row): within `tol` a match,
+    else the smaller one steps.  A maximum matching for a symmetric tolerance."""
+    i = j = 0
+    out = []
+    while i < len(R) and j < len(D):
+        if abs(D[j][0] - R[i][0]) <= tol:
+            out.append((D[j][1], R[i][1]))
+            i += 1
+            j += 1
+        elif D[j][0] < R[i][0]:
+            j += 1
+        else:
+            i += 1
+    return out
+
+
+def score(table: Optional[Dict], ref_table: Optional[Dict], tol_sec: float = 0.05, gap_sec: float = 5.0) -> Dict:
+    """The detected marks of one recording (`table`: a labels dict's
+    ``table``, or None where the analysis made no labels) scored against a
+    person's corrected marks (`ref_table`: a label table, or the dict of
+    ``marks_from_table``).
+
+    Labelled spans: the reference marks of both types together; a new span
+    starts where the step is >= gap; a span is [first - tol, last + tol].  A
+    detected mark in no span is outside.  Pass 1, per type: the walk of the
+    in-span detected marks against the reference marks of the type: TP.  Pass
+    2, per type: the detected marks left against the reference marks of the
+    other type left: SWAP.  What is left: FP (detected), FN (reference).
+
+    Returns ``record`` (int64[20], ``SR_*``), ``status`` and the rows
+    ``sc_kind`` / ``sc_ref`` per detected mark and ``rf_kind`` / ``rf_det``
+    per reference mark (int32; empty with ``SCORE_NONE``: no reference mark),
+    plus ``marks`` and ``det_ms``."""
+    tol, gap = score_ms(tol_sec, gap_sec)
+    marks = ref_table if ref_table is not None and "ms" in ref_table else marks_from_table(ref_table)
+    status = SCORE_OK if table is not None else SCORE_NO_LABELS
+    dms = _ms(table["time"]).tolist() if table is not None else []
+    dty = np.asarray(table["type"]).astype(np.int64).tolist() if table is not None else []
+    rms, rty = marks["ms"].tolist(), marks["type"].tolist()
+    nd, nr = len(dms), len(rms)
+    rec = np.zeros(SCORE_RECORD, np.int64)
+    e32 = np.zeros(0, np.int32)
+    out = {"record": rec, "status": status, "sc_kind": e32, "sc_ref": e32, "rf_kind": e32, "rf_det": e32,
+           "marks": marks, "det_ms": np.asarray(dms, np.int32), "tol_ms": tol, "gap_ms": gap}
+    if nr == 0:
+        rec[SR_N_OUTSIDE] = nd
+        out["status"] = SCORE_NONE
+        return out
+    spans = []
+    for i, m in enumerate(rms):
+        if i == 0 or m - rms[i - 1] >= gap:
+            spans.append([m, m])
+        spans[-1][1] = m
+    inside = [any(a - tol <= d <= z + tol for a, z in spans) for d in dms]
+    sc_kind = [KIND_FP if inside[j] and dty[j] in (S1, S2) else KIND_OUTSIDE for j in range(nd)]
+    rf_kind = [KIND_FN if rty[i] in (S1, S2) else KIND_OUTSIDE for i in range(nr)]
+    sc_ref, rf_det = [-1] * nd, [-1] * nr
+    for kind in (KIND_TP, KIND_SWAP):
+        for k, typ in enumerate((S1, S2)):
+            other = typ if kind == KIND_TP else (S2 if typ == S1 else S1)
+            D = [(dms[j], j) for j in range(nd) if sc_kind[j] == KIND_FP and dty[j] == typ]
+            R = [(rms[i], i) for i in range(nr) if rf_kind[i] == KIND_FN and rty[i] == other]
+            for j, i in _walk(D, R, tol):
+                sc_kind[j], sc_ref[j], rf_kind[i], rf_det[i] = kind, i, kind, j
+                if kind == KIND_TP:
+                    e = dms[j] - rms[i]
+                    r = rec[k * SR_PER_TYPE:]
+                    r[SR_SUM_ERR] += e
+                    r[SR_SUM_ABS] += abs(e)
+                    r[SR_MAX_ABS] = max(int(r[SR_MAX_ABS]), abs(e))
+    for k, typ in enumerate((S1, S2)):
+        r = rec[k * SR_PER_TYPE:]
+        mine = [sc_kind[j] for j in range(nd) if dty[j] == typ and sc_kind[j] != KIND_OUTSIDE]
+        theirs = [rf_kind[i] for i in range(nr) if rty[i] == typ]
+        r[SR_N_REF], r[SR_N_DET] = len(theirs), len(mine)
+        r[SR_TP], r[SR_SWAP], r[SR_FP] = mine.count(KIND_TP), mine.count(KIND_SWAP), mine.count(KIND_FP)
+        r[SR_FN] = theirs.count(KIND_FN)
+    rec[SR_N_OUTSIDE] = sc_kind.count(KIND_OUTSIDE)
+    rec[SR_N_SPANS] = len(spans)
+    out.update(sc_kind=np.asarray(sc_kind, np.int32), sc_ref=np.asarray(sc_ref, np.int32),
+               rf_kind=np.asarray(rf_kind, np.int32), rf_det=np.asarray(rf_det, np.int32))
+    return out
+
+
+def _ratio(a, b) -> float:
+    return float(a) / float(b) if b else float("nan")
+
+
+def score_summary(record) -> Dict:
+    """Precision, recall, F1 and the mean errors in seconds from one integer
+    record (a file's, or the sum of many files' with ``MAX_ABS`` their
+    maximum: ``score_total``).  Per type (``"S1"``, ``"S2"``) and ``"all"``
+    (both types added); ``n_outside`` and ``n_spans``.  A division by zero
+    gives NaN."""
+    rec = np.asarray(record, dtype=np.int64).reshape(SCORE_RECORD)
+    parts = {"S1": rec[:SR_PER_TYPE], "S2": rec[SR_PER_TYPE:2 * SR_PER_TYPE]}
+    both = parts["S1"] + parts["S2"]
+    both[SR_MAX_ABS] = max(int(parts["S1"][SR_MAX_ABS]), int(parts["S2"][SR_MAX_ABS]))
+    parts["all"] = both
+    out: Dict = {"n_outside": int(rec[SR_N_OUTSIDE]), "n_spans": int(rec[SR_N_SPANS])}
+    for name, r in parts.items():
+        tp = int(r[SR_TP])
+        p, q = _ratio(tp, r[SR_N_DET]), _ratio(tp, r[SR_N_REF])
+        f1 = 2 * p * q / (p + q) if p + q > 0 else (float("nan") if p != p or q != q else 0.0)
+        out[name] = {"n_ref": int(r[SR_N_REF]), "n_det": int(r[SR_N_DET]), "tp": tp, "swap": int(r[SR_SWAP]),
+                     "fp": int(r[SR_FP]), "fn": int(r[SR_FN]), "precision": p, "recall": q, "f1": f1,
+                     "mean_err_sec": _ratio(r[SR_SUM_ERR], tp) / 1000.0,
+                     "mean_abs_err_sec": _ratio(r[SR_SUM_ABS], tp) / 1000.0,
+                     "max_abs_err_sec": float(r[SR_MAX_ABS]) / 1000.0 if tp else float("nan")}
+    return out
+
+
+def score_total(records) -> np.ndarray:
+    """The record of many files: every field added, ``MAX_ABS`` the maximum."""
+    r = np.asarray(records, dtype=np.int64).reshape(-1, SCORE_RECORD)
+    tot = r.sum(axis=0)
+    for k in (SR_MAX_ABS, SR_PER_TYPE + SR_MAX_ABS):
+        tot[k] = r[:, k].max() if len(r) else 0
+    return tot
+
+
+def score_csv_text(table: Optional[Dict], result: Dict) -> str:
+    """The list of mistakes of one recording: one row per mark that is not a
+    TP, ascending in time: the detected marks outside every span, swapped and
+    false (``OUTSIDE``, ``SWAP``, ``FP``) and the reference marks missed
+    (``FN``), with the partner's time for a SWAP.  `result`: ``score``'s dict,
+    or ``Scores.to_host``'s with ``marks``."""
+    marks = result["marks"]
+    rows = []
+    if table is not None and len(result["sc_kind"]):
+        for j, (t, k) in enumerate(zip(np.asarray(table["time"]).tolist(), np.asarray(table["type"]).tolist())):
+            kind, i = int(result["sc_kind"][j]), int(result["sc_ref"][j])
+            if kind != KIND_TP:
+                rows.append((t, 0, f"{repr(t)},{TYPE_NAME.get(int(k), k)},{KIND_NAME[kind]},"
+                                   f"{repr(float(marks['time'][i])) if i >= 0 else ''}\n"))
+    for i, kind in enumerate(np.asarray(result["rf_kind"]).tolist()):
+        if kind == KIND_FN:
+            t = float(marks["time"][i])
+            rows.append((t, 1, f"{repr(t)},{TYPE_NAME[int(marks['type'][i])]},FN,\n"))
+    rows.sort(key=lambda r: (r[0], r[1]))
+    return ",".join(SCORE_COLUMNS) + "\n" + "".join(r[2] for r in rows)

@@ -28,6 +28,8 @@
  *   bpmx_labels_device         <- heartbeat_labeler.py  the labeler's output from the beat stages'
  *                                 decisions: the S1 / S2 table of <base>_labels.csv (:530-546), the
  *                                 S1-S2 pairs (:198-217), the groups and their statistics (:244-308)
+ *   bpmx_score_device          (no counterpart in the reference: defined here)  the label rows scored
+ *                                 against a person's corrected <base>_labels.csv: TP, SWAP, FP, FN
  *   bpmx_synth / bpmx_synth_host   deterministic synthetic recordings (bench/tests)
  *
  * Plain C types only.  PCM and result arrays are DEVICE pointers (HBM); the
@@ -51,7 +53,8 @@ extern "C" {
 #endif
 
 /* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
- * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL. */
+ * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL;
+ * bpmx_score_device and BPMX_OPT_SCORE_GLOBAL. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
@@ -164,6 +167,8 @@ enum bpmx_option {
     BPMX_OPT_RECT_SEQ = 65536,       /* rectified mode: the general route (the pandas recursion, one lane per
                                         recording) for every recording, also where the exact-integer route
                                         applies (test/diagnostic) */
+    BPMX_OPT_SCORE_GLOBAL = 262144,  /* bpmx_score_device (set with bpmx_set_options): every recording's
+                                        workspace in global memory instead of LDS (test/diagnostic) */
     BPMX_OPT_LABELS_GLOBAL = 131072  /* bpmx_labels_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS (test/diagnostic) */
 };
@@ -598,8 +603,95 @@ int bpmx_labels_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_la
                        const bpmx_packed *tables, const bpmx_beats_out *beats, const int32_t *gap,
                        const bpmx_labels_out *out, void *stream);
 
+/* Beats scored against corrected labels on the device (bpmx_score_device).
+ *
+ * Once a person has corrected the marks of <base>_labels.csv in the labeler,
+ * the question is how well some settings reproduce them.  The reference has no
+ * scoring; this is the definition (csrc/bpmx_score_core.h states it for host
+ * and device, labels.score in Python).  Everything is integer milliseconds.
+ *
+ *   Detected marks: the label rows of bpmx_labels_device (lb_time, lb_type,
+ *       n_labels, ascending), ms = llrint(lb_time * 1000.0) saturated to
+ *       int32.  A labels status other than BPMX_LABELS_OK gives an empty list
+ *       and sets the bit BPMX_SCORE_NO_LABELS.
+ *   Reference marks: the S1 / S2 rows of the corrected file, prepared on the
+ *       host (labels.marks_from_table): ms = rint(time * 1000), sorted stably
+ *       by ms, uploaded as a ragged table.
+ *   Spans: the reference marks of both types together; a new span starts
+ *       where the step is >= gap_ms; a span is [first - tol_ms, last + tol_ms].
+ *       A detected mark in no span is outside: counted, scored no further.
+ *   The walk over two ascending lists D, R from i = j = 0: |D[j] - R[i]| <=
+ *       tol_ms is a match (both step), else the smaller one steps.  It gives a
+ *       maximum matching.
+ *   Pass 1, per type: the in-span detected marks of the type against the
+ *       reference marks of the type: TP, with the error e = D - R.
+ *   Pass 2, per type: the detected marks left against the reference marks of
+ *       the other type left: SWAP (the beat was heard, but given the other
+ *       name).  A detected mark still unmatched is FP, a reference mark FN.
+ *
+ * N_DET = TP + SWAP + FP, N_REF = TP + SWAP[other type] + FN and
+ * N_OUTSIDE + N_DET[S1] + N_DET[S2] = n_labels.  Precision, recall and the
+ * mean errors are left to the host (labels.score_summary). */
+typedef struct {
+    int32_t tol_ms;             /* >= 0: two marks this close are the same beat */
+    int32_t gap_ms;             /* > 2 * tol_ms: a pause this long between reference marks ends a labelled span */
+} bpmx_score_params;
+
+typedef struct {
+    int64_t cap_ref;            /* capacity of rf_ms / rf_type and of the rf_* outputs, entries */
+    const int64_t *rf_off;      /* [n_files + 1] ascending */
+    const int32_t *rf_ms;       /* [cap_ref] ascending within a file */
+    const int32_t *rf_type;     /* [cap_ref] bpmx_label_type; any other value takes part in the spans only */
+} bpmx_ref_marks;
+
+enum bpmx_score_kind {          /* sc_kind; rf_kind (0 there: a type that is neither S1 nor S2) */
+    BPMX_SCORE_OUTSIDE = 0, BPMX_SCORE_TP = 1, BPMX_SCORE_SWAP = 2, BPMX_SCORE_FP = 3, BPMX_SCORE_FN = 3
+};
+
+enum bpmx_score_status {        /* bpmx_score_out.status: 0, the bit, or a negative code */
+    BPMX_SCORE_OK = 0,
+    BPMX_SCORE_NO_LABELS = 1,   /* bit: the labels stage made no labels; every reference mark is an FN */
+    BPMX_SCORE_NONE = -22,      /* no reference mark: the record is zeros apart from N_OUTSIDE = n_labels, no rows
+                                   are written */
+    BPMX_SCORE_OVERFLOW = -23   /* a slice reaches past cap_peaks or cap_ref, or rf_off is not ascending: nothing
+                                   written but the status */
+};
+
+/* bpmx_score_out.record: 20 int64 per file; nine fields for S1, nine for S2, two for the file */
+enum bpmx_score_record {
+    BPMX_SR_N_REF = 0,          /* reference marks of the type */
+    BPMX_SR_N_DET = 1,          /* detected marks of the type in a span */
+    BPMX_SR_TP = 2, BPMX_SR_SWAP = 3, /* SWAP: detected as this type, matched to a reference mark of the other */
+    BPMX_SR_FP = 4, BPMX_SR_FN = 5,
+    BPMX_SR_SUM_ERR = 6,        /* over the TP: sum of e, sum of |e|, largest |e| (0 without TP), ms */
+    BPMX_SR_SUM_ABS = 7, BPMX_SR_MAX_ABS = 8,
+    BPMX_SR_PER_TYPE = 9,       /* the S2 fields start here */
+    BPMX_SR_N_OUTSIDE = 18, BPMX_SR_N_SPANS = 19,
+    BPMX_SCORE_RECORD = 20
+};
+
+typedef struct {
+    int32_t *sc_kind, *sc_ref;  /* [cap_peaks] per label row, slices at pk_off[f]: bpmx_score_kind, the matched
+                                   reference row within the file or -1 */
+    int32_t *rf_kind, *rf_det;  /* [cap_ref] per reference row, slices at rf_off[f]: bpmx_score_kind, the matched
+                                   label row or -1 */
+    int64_t *record;            /* [n_files][BPMX_SCORE_RECORD] */
+    int32_t *status;            /* [n_files] bpmx_score_status */
+} bpmx_score_out;
+
+/* The scores of n_files recordings: `labels` (lb_time, lb_type, n_labels and
+ * status of bpmx_labels_device over `tables`, of which pk_off and cap_peaks are
+ * read) against `ref`, asynchronously on `stream`, ordered after the labels
+ * stage.  Never synchronises the host; scratch comes from ctx.  The four row
+ * pointers of `out` are optional as a group (all NULL: record and status
+ * only); nothing outside a file's used entries is written.  n_files = 0 does
+ * nothing.  One workgroup per recording; see csrc/k_score.hip. */
+int bpmx_score_device(bpmx_ctx *ctx, int32_t n_files, const bpmx_score_params *params, const bpmx_packed *tables,
+                      const bpmx_labels_out *labels, const bpmx_ref_marks *ref, const bpmx_score_out *out,
+                      void *stream);
+
 /* bpmx_option bits for the entry points that take no bpmx_params
- * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL);
+ * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL, BPMX_OPT_SCORE_GLOBAL);
  * they hold until set again. */
 int bpmx_set_options(bpmx_ctx *ctx, int32_t options);
 
