@@ -29,7 +29,7 @@ constexpr int HB_MF_UNITS = 2;             /* 16 x 16 output tiles per wave in s
  * (exact floor).  The plan's divisors times the kernel's dividends stay
  * below 2^32 (hilbert_plan checks M). */
 __host__ __device__ inline uint64_t hb_magic(uint32_t d) { return 0xFFFFFFFFull / d + 1ull; }
-__device__ __forceinline__ int hb_div(int x, uint64_t m) { return (int)(((uint64_t)(uint32_t)x * m) >> 32); }
+__host__ __device__ __forceinline__ int hb_div(int x, uint64_t m) { return (int)(((uint64_t)(uint32_t)x * m) >> 32); }
 
 struct HilbPlan {
     int32_t M, N, ns, ntwh, nptab, window;

@@ -634,6 +634,41 @@ static bool lf_shape(int64_t M, int32_t *A, int32_t *B) {
     return true;
 }
 
+/* the row plan of an n-point sub-DFT, without its table offsets: direct
+ * (Stockham radices of n), Rader (prime n, smooth n - 1) or Bluestein */
+static LfSub lf_sub_shape(int32_t n) {
+    LfSub sb{};
+    sb.n = n;
+    std::vector<int> rd, rp;
+    const bool direct = radices(n, rd);
+    const bool rader = !direct && radices(n - 1, rp) && primitive_root(n) > 0;
+    sb.kind = direct ? 0 : (rader ? 2 : 1);
+    if (direct) {
+        sb.L = 0;
+        sb.rpw = std::max(1, LF_GROUP / n);
+    } else if (rader) {
+        const int32_t P = n - 1;
+        /* rows per workgroup: LF_GROUP points, within ~144 KB of LDS */
+        sb.rpw = std::max(1, std::min({LF_GROUP / P, (9216 - P) / (n + P), 64}));
+        sb.L = P;
+        rd = rp;
+    } else {
+        sb.rpw = 1;
+        /* the shortest 2^a 3^b 5^c >= 2n - 1 (power-of-two padding would
+         * cost ~40 % more butterflies over C5's lengths) */
+        int32_t L = 0;
+        for (int64_t p2 = 1; p2 <= LF_LMAX; p2 *= 2)
+            for (int64_t p3 = p2; p3 <= LF_LMAX; p3 *= 3)
+                for (int64_t p5 = p3; p5 <= LF_LMAX; p5 *= 5)
+                    if (p5 >= 2 * n - 1 && (L == 0 || p5 < L)) L = (int32_t)p5;
+        sb.L = L;
+        radices(L, rd);
+    }
+    sb.nrad = (int32_t)rd.size();
+    for (int i = 0; i < sb.nrad; ++i) sb.rad[i] = rd[i];
+    return sb;
+}
+
 bool longfft_supported(int64_t N) {
     if (N < 64 || N > 2 * (int64_t)LF_NMAX * LF_NMAX) return false;
     const int64_t M = (N % 2 == 0) ? N / 2 : N;
@@ -662,12 +697,7 @@ int longfft_hilbert(bpmx_ctx *ctx, hipStream_t s, const double *yd, double *hb, 
         auto get_sub = [&](int32_t n) -> int32_t {
             auto it = sub_of.find(n);
             if (it != sub_of.end()) return it->second;
-            LfSub sb{};
-            sb.n = n;
-            std::vector<int> rd, rp;
-            const bool direct = radices(n, rd);
-            const bool rader = !direct && radices(n - 1, rp) && primitive_root(n) > 0;
-            sb.kind = direct ? 0 : (rader ? 2 : 1);
+            LfSub sb = lf_sub_shape(n);
             sb.toff = tabsz;
             tabs.push_back(LfTab{tabsz, n, sb.kind == 1 ? 1 : 0, n, 0});    /* roots of n, or chirps */
             tabsz += n;
@@ -680,16 +710,9 @@ int longfft_hilbert(bpmx_ctx *ctx, hipStream_t s, const double *yd, double *hb, 
                 }
                 return lt->second;
             };
-            if (direct) {
-                sb.L = 0;
-                sb.rpw = std::max(1, LF_GROUP / n);
-            } else if (rader) {
+            if (sb.kind == 2) {
                 /* g^q and g^-q mod n; the convolution kernels' spectra at fb (forward, inverse) */
-                const int32_t P = n - 1, g = primitive_root(n);
-                /* rows per workgroup: LF_GROUP points, within ~144 KB of LDS */
-                sb.rpw = std::max(1, std::min({LF_GROUP / P, (9216 - P) / (n + P), 64}));
-                sb.L = P;
-                rd = rp;
+                const int32_t P = sb.L, g = primitive_root(n);
                 sb.loff = roots_of(P);
                 sb.ioff = (int64_t)itab.size();
                 std::vector<int32_t> pw(P);
@@ -700,24 +723,12 @@ int longfft_hilbert(bpmx_ctx *ctx, hipStream_t s, const double *yd, double *hb, 
                 sb.fb = fbsz;
                 fbsz += 2 * P;
                 rad.push_back((int32_t)subs.size());
-            } else {
-                sb.rpw = 1;
-                /* the shortest 2^a 3^b 5^c >= 2n - 1 (power-of-two padding would
-                 * cost ~40 % more butterflies over C5's lengths) */
-                int32_t L = 0;
-                for (int64_t p2 = 1; p2 <= LF_LMAX; p2 *= 2)
-                    for (int64_t p3 = p2; p3 <= LF_LMAX; p3 *= 3)
-                        for (int64_t p5 = p3; p5 <= LF_LMAX; p5 *= 5)
-                            if (p5 >= 2 * n - 1 && (L == 0 || p5 < L)) L = (int32_t)p5;
-                sb.L = L;
-                radices(L, rd);
-                sb.loff = roots_of(L);
+            } else if (sb.kind == 1) {
+                sb.loff = roots_of(sb.L);
                 sb.fb = fbsz;
-                fbsz += L;
+                fbsz += sb.L;
                 blu.push_back((int32_t)subs.size());
             }
-            sb.nrad = (int32_t)rd.size();
-            for (int i = 0; i < sb.nrad; ++i) sb.rad[i] = rd[i];
             subs.push_back(sb);
             return sub_of[n] = (int32_t)subs.size() - 1;
         };

@@ -1206,9 +1206,12 @@ def test_config_c5_shard_of_eight(det):
 def test_longfft_hilbert_matches_bluestein_and_oracle(det):
     """Long recordings' Hilbert transform by exact-length four-step DFTs
     (k_longfft.hip) against the rocFFT Bluestein path (BPMX_OPT_HILBERT_BLUESTEIN)
-    and the oracle: lengths with a large prime row (s = 601, 1201: Bluestein
-    rows inside the workgroup; s = 1742 = 2 x 13 x 67: 4160-point rows), a
-    smooth one (s = 1800) and an odd Nd (unpacked transform), 96 kHz mono."""
+    and the oracle, 96 kHz mono (ds = 300).  The rows, as
+    tests/hilbert_plan_driver.hip prints them: Nd = 192,320 (601 s): Rader rows
+    of 601 points, direct rows of 160; Nd = 278,720 (871 s): Rader rows of 67
+    points, direct rows of 2,080 (one per workgroup); Nd = 95,993 = 59 x 1627,
+    odd, so unpacked: in-workgroup Bluestein rows of 1,627 points (L = 3,375),
+    direct rows of 59; Nd = 192,000 (600 s), smooth: direct rows of 300 and 320."""
     import torch
     from bpm_analysis_amd import _native as N
     fs = 96000
