@@ -41,6 +41,7 @@ OPT_METRICS_GLOBAL = 32768         # bpmx_metrics_device, through bpmx_set_optio
 OPT_RECT_SEQ = 65536               # rectified mode: the pandas recursion for every recording (test/diagnostic)
 OPT_LABELS_GLOBAL = 131072          # bpmx_labels_device, through bpmx_set_options (test/diagnostic)
 OPT_SCORE_GLOBAL = 262144           # bpmx_score_device, through bpmx_set_options (test/diagnostic)
+OPT_MARKS_GLOBAL = 524288           # bpmx_marks_device, through bpmx_set_options (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS
@@ -58,6 +59,9 @@ SCORE_OK, SCORE_NO_LABELS, SCORE_NONE, SCORE_OVERFLOW = 0, 1, -22, -23
 SCORE_OUTSIDE, SCORE_TP, SCORE_SWAP, SCORE_FP, SCORE_FN = 0, 1, 2, 3, 3
 SR_N_REF, SR_N_DET, SR_TP, SR_SWAP, SR_FP, SR_FN, SR_SUM_ERR, SR_SUM_ABS, SR_MAX_ABS = 0, 1, 2, 3, 4, 5, 6, 7, 8
 SR_PER_TYPE, SR_N_OUTSIDE, SR_N_SPANS, SCORE_RECORD = 9, 18, 19, 20
+# bpmx_marks_device: the two statuses it adds to bpmx_beats_out.status, and its record (8 int32 per file)
+MARKS_FEW, MARKS_OVERFLOW = -24, -25
+MK_N_ROWS, MK_N_S1, MK_N_S2, MK_N_MERGED, MK_N_DROPPED, MK_N_OTHER, MARKS_RECORD = 0, 1, 2, 3, 4, 5, 8
 # bpmx_trace_out.record (bpmx_trace_field: 18 doubles per raw peak), .code (bpmx_trace_code) and .gap
 TR_BLEND, TR_BASE_CONF, TR_STAB_FACTOR, TR_STAB_RATIO, TR_ADJ_AMOUNT, TR_ADJ_RATIO, TR_ADJ_RMAX = 0, 1, 2, 3, 4, 5, 6
 TR_IV_AMOUNT, TR_IV_GAP, TR_IV_CAP, TR_FINAL = 7, 8, 9, 10
@@ -70,7 +74,7 @@ EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
            "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
            "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot",
-           "bpmx_labels_device", "bpmx_score_device"]
+           "bpmx_labels_device", "bpmx_score_device", "bpmx_marks_device"]
 
 
 class Params(ctypes.Structure):
@@ -180,6 +184,11 @@ class ScoreOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("sc_kind", "sc_ref", "rf_kind", "rf_det", "record", "status")]
 
 
+class MarksParams(ctypes.Structure):
+    """bpmx_marks_params: the curve's smoothing window (output_smoothing_window_sec), seconds."""
+    _fields_ = [("smoothing_window_sec", ctypes.c_double)]
+
+
 class BpmxError(RuntimeError):
     """A libbpmx failure.  ``code`` is the BPMX_E_* status (None when raised by
     the host side).  Only argument and size-limit errors belong to the
@@ -279,6 +288,10 @@ def load() -> ctypes.CDLL:
                                         ctypes.POINTER(LabelsOut), ctypes.POINTER(RefMarks),
                                         ctypes.POINTER(ScoreOut), P]
         L.bpmx_score_device.restype = ctypes.c_int
+    if hasattr(L, "bpmx_marks_device"):
+        L.bpmx_marks_device.argtypes = [P, I32, I32, ctypes.POINTER(MarksParams), ctypes.POINTER(RefMarks), P,
+                                        ctypes.POINTER(PackedOut), ctypes.POINTER(BeatsOut), P, P, P]
+        L.bpmx_marks_device.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

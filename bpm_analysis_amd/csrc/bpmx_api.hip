@@ -2,8 +2,8 @@
  * bpmx_api.hip — host side of the C ABI (include/bpmx.h): context, scratch,
  * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
  * bpmx_pack_trough_floor, bpmx_pack_plot, bpmx_beats_device,
- * bpmx_beats_device_ex, bpmx_metrics_device, bpmx_labels_device and
- * bpmx_score_device.
+ * bpmx_beats_device_ex, bpmx_metrics_device, bpmx_labels_device,
+ * bpmx_score_device and bpmx_marks_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -137,6 +137,32 @@ int score_stage(bpmx_ctx *ctx, const ScorePlan &S, int32_t n_files, const bpmx_s
         if (rc != BPMX_OK) return rc;
     }
     LAUNCH(ctx, s, "k_score", k_score, dim3(S.grid), dim3(SCORE_T), S.lds, s, a);
+    return BPMX_OK;
+}
+
+/* a person's marks as tables, beats and curve: three launches sized by the plan */
+int marks_stage(bpmx_ctx *ctx, const MarksPlan &M, int32_t n_files, int32_t sr, const bpmx_marks_params &P,
+                const bpmx_ref_marks &r, const int64_t *nd, const bpmx_packed &t, const bpmx_beats_out &b,
+                int32_t *gap, int32_t *record, hipStream_t s) {
+    int rc = BPMX_OK;
+    MarksArgs a{};
+    a.n_files = n_files; a.sr = sr; a.cap = t.cap_peaks; a.cap_ref = r.cap_ref; a.lds_n = M.lds_n; a.fixed = M.fixed;
+    a.window_sec = P.smoothing_window_sec;
+    a.rf_off = r.rf_off; a.rf_ms = r.rf_ms; a.rf_type = r.rf_type; a.nd = nd;
+    unsigned char *rows = (unsigned char *)ctx->buf("marks_rows", M.rows, &rc);
+    if (rc != BPMX_OK) return rc;
+    a.k_idx = (int32_t *)rows; a.r_idx = (int32_t *)(rows + M.o_ridx);
+    a.k_type = (int8_t *)(rows + M.o_ktype); a.r_tag = (int8_t *)(rows + M.o_rtag);
+    a.cnt = (int32_t *)(rows + M.o_cnt);
+    if (M.any_global) {
+        a.gws = (unsigned char *)ctx->buf("marks_ws", M.gws, &rc);
+        if (rc != BPMX_OK) return rc;
+    }
+    a.pk_off = t.pk_off; a.pk_idx = t.pk_idx; a.pk_env = t.pk_env; a.pk_floor = t.pk_floor;
+    a.B = b; a.gap = gap; a.record = record;
+    LAUNCH(ctx, s, "k_marks_rows", k_marks_rows, dim3(M.grid), dim3(MARKS_T), 0, s, a);
+    LAUNCH(ctx, s, "k_marks_scan", k_marks_scan, dim3(1), dim3(MARKS_T), 0, s, a);
+    LAUNCH(ctx, s, "k_marks_finish", k_marks_finish, dim3(M.grid), dim3(MARKS_T), M.lds, s, a);
     return BPMX_OK;
 }
 
@@ -758,6 +784,30 @@ int bpmx_score_device(bpmx_ctx *ctx, int32_t n_files, const bpmx_score_params *p
     HIP_TRY(hipSetDevice(ctx->device));
     return score_stage(ctx, score_plan(n_files, tables->cap_peaks, ref->cap_ref, ctx->options), n_files, *params,
                        *tables, *labels, *ref, *out, (hipStream_t)stream);
+}
+
+int bpmx_marks_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_marks_params *params,
+                      const bpmx_ref_marks *marks, const int64_t *nd, const bpmx_packed *tables,
+                      const bpmx_beats_out *beats, int32_t *gap, int32_t *record, void *stream) {
+    if (!ctx || !params || !marks || !tables || !beats || !gap || !record)
+        return fail(BPMX_E_ARG, "bpmx_marks_device: NULL argument (gap and record are required)");
+    if (n_files < 0 || sr < 1) return fail(BPMX_E_ARG, "bpmx_marks_device: bad n_files/sr");
+    if (!(params->smoothing_window_sec > 0))
+        return fail(BPMX_E_ARG, "bpmx_marks_device: needs smoothing_window_sec > 0");
+    if (n_files == 0) return BPMX_OK;
+    if (!marks->rf_off || marks->cap_ref < 0 || marks->cap_ref >= (int64_t)INT_MAX ||
+        (marks->cap_ref > 0 && (!marks->rf_ms || !marks->rf_type)))
+        return fail(BPMX_E_ARG, "bpmx_marks_device: needs rf_off, 0 <= cap_ref < 2^31 and, with cap_ref > 0, rf_ms "
+                                "and rf_type");
+    if (!tables->pk_off || !tables->pk_idx || tables->cap_peaks < 0 || tables->cap_peaks >= (int64_t)INT_MAX)
+        return fail(BPMX_E_ARG, "bpmx_marks_device: needs pk_off, pk_idx and 0 <= cap_peaks < 2^31");
+    if (!beats->final_idx || !beats->n_final || !beats->bpm_t || !beats->bpm || !beats->n_bpm || !beats->tags ||
+        !beats->status)
+        return fail(BPMX_E_ARG, "bpmx_marks_device: the beats' final_idx, n_final, bpm_t, bpm, n_bpm, tags and "
+                                "status are required");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return marks_stage(ctx, marks_plan(n_files, marks->cap_ref, ctx->options), n_files, sr, *params, *marks, nd,
+                       *tables, *beats, gap, record, (hipStream_t)stream);
 }
 
 }  // extern "C"

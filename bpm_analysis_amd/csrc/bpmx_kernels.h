@@ -619,6 +619,33 @@ struct ScoreArgs {
 };
 __global__ void k_score(ScoreArgs A);
 
+/* bpmx_marks_device (k_marks.hip): rows per recording, the scan of the row
+ * counts into pk_off, then tables, beats and curve per recording */
+enum { MARKS_T = 256 };
+struct MarksArgs {
+    int32_t n_files, sr;
+    int64_t cap, cap_ref;       /* capacities of the peak table and of the marks, entries */
+    int64_t lds_n;              /* a recording of at most this many S1 rows works in LDS (-1: none) */
+    size_t fixed;               /* marks_ws_fixed(MARKS_T): a global slice starts at f * fixed + MK_STRIDE * rf_off[f] */
+    double window_sec;
+    const int64_t *rf_off;      /* [F+1] */
+    const int32_t *rf_ms, *rf_type;
+    const int64_t *nd;          /* optional [F] */
+    /* context scratch: the kept marks and the rows at the rf_off slices, the counts per file */
+    int32_t *k_idx, *r_idx;     /* [cap_ref] */
+    int8_t *k_type, *r_tag;     /* [cap_ref] */
+    int32_t *cnt;               /* [F][MC_PER_FILE] */
+    unsigned char *gws;         /* workspaces of the recordings beyond lds_n (bpmx_plan.h marks_plan) */
+    int64_t *pk_off;            /* [F+1] */
+    int32_t *pk_idx;
+    double *pk_env, *pk_floor;  /* optional */
+    bpmx_beats_out B;
+    int32_t *gap, *record;
+};
+__global__ void k_marks_rows(MarksArgs A);
+__global__ void k_marks_scan(MarksArgs A);
+__global__ void k_marks_finish(MarksArgs A);
+
 /* Rectified-mode envelope (k_rect.hip): the centred rolling mean of |x| at the
  * native rate.  Integer PCM of one or two channels takes the exact-integer
  * route (window sums from int64 prefix sums, one division); everything else

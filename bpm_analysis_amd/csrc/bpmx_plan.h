@@ -15,6 +15,7 @@
 #include "bpmx_metrics_core.h"
 #include "bpmx_labels_core.h"
 #include "bpmx_score_core.h"
+#include "bpmx_marks_core.h"
 #include "bpmx_rect_core.h"
 #include "bpmx_kernels.h"
 
@@ -374,6 +375,46 @@ inline ScorePlan score_plan(int F, int64_t cap_peaks, int64_t cap_ref, int32_t o
     S.fixed = score_ws_fixed(SCORE_T);
     S.gws = S.any_global ? (size_t)F * S.fixed + (size_t)(cap_peaks + cap_ref) * SC_STRIDE : 0;
     return S;
+}
+
+/* bpmx_marks_device: three launches (k_marks.hip).  k_marks_rows and
+ * k_marks_finish run one workgroup of MARKS_T threads per recording; the row
+ * scratch (MK_SCRATCH bytes per mark) and the counts are one context buffer.
+ * k_marks_finish' workspace (bpmx_marks_core.h: the lane counts and
+ * beats_series' 47 bytes per S1 row) lives in LDS when it fits
+ * MARKS_LDS_BUDGET: 32 KB, so five workgroups share a CU's 160 KB, and the
+ * 605 beats a 60 s recording can have are inside it.  Longer tables take a
+ * slice of one global buffer at f * fixed + MK_STRIDE * rf_off[f].  Sized
+ * from the marks' capacity and the file count alone. */
+constexpr size_t MARKS_LDS_BUDGET = 32 * 1024;
+
+struct MarksPlan {
+    unsigned grid;              /* workgroups of the two per-recording launches */
+    int64_t lds_n;              /* most S1 rows of an LDS-path recording (-1: every recording goes global) */
+    size_t lds;                 /* dynamic LDS bytes per workgroup of k_marks_finish */
+    bool any_global;
+    size_t fixed;               /* marks_ws_fixed(MARKS_T) */
+    size_t gws;                 /* bytes of the global workspace buffer (0: none) */
+    size_t rows;                /* bytes of the row scratch: k_idx, r_idx, k_type, r_tag, cnt in this order */
+    size_t o_ridx, o_ktype, o_rtag, o_cnt;   /* their offsets (k_idx at 0) */
+};
+
+inline MarksPlan marks_plan(int F, int64_t cap_ref, int32_t options, size_t budget = MARKS_LDS_BUDGET) {
+    MarksPlan M{};
+    M.grid = (unsigned)F;
+    const bool forced = (options & BPMX_OPT_MARKS_GLOBAL) != 0;
+    M.lds_n = forced ? -1 : std::min<int64_t>(cap_ref, marks_ws_max_n(budget, MARKS_T));
+    M.lds = M.lds_n < 0 ? 0 : marks_ws_bytes(M.lds_n, MARKS_T);
+    M.any_global = cap_ref > M.lds_n;
+    M.fixed = marks_ws_fixed(MARKS_T);
+    M.gws = M.any_global ? (size_t)F * M.fixed + (size_t)cap_ref * MK_STRIDE : 0;
+    const size_t c8 = (size_t)beats_n8(cap_ref);
+    M.o_ridx = 4 * c8;
+    M.o_ktype = 8 * c8;
+    M.o_rtag = 9 * c8;
+    M.o_cnt = 10 * c8;
+    M.rows = M.o_cnt + (size_t)F * MC_PER_FILE * 4;
+    return M;
 }
 
 }  // namespace bpmx

@@ -514,6 +514,169 @@ def score_wav_files(file_paths: Sequence[str], params_list: Sequence[Dict], labe
     return out
 
 
+def _label_rates(n: int, sample_rates, wav_paths, params: Dict, mode: str) -> List:
+    """The decimated rate of every label file: an int for all, one per file,
+    or from the headers of `wav_paths` (the rate the analysis of that WAV
+    runs at).  An entry that cannot be had is the exception."""
+    if wav_paths is not None:
+        from scipy.io import wavfile
+        if len(wav_paths) != n:
+            raise ValueError("wav_paths needs one entry per label file")
+        out = []
+        for p in wav_paths:
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    fs, _ = wavfile.read(p, mmap=True)
+                out.append(int(mode_design(int(fs), params, mode).sr))
+            except Exception as exc:                  # per file, as in the GUI loop
+                out.append(exc)
+        return out
+    if sample_rates is None:
+        raise ValueError("sample_rates or wav_paths is required")
+    if np.ndim(sample_rates) == 0:
+        return [int(sample_rates)] * n
+    if len(sample_rates) != n:
+        raise ValueError("sample_rates needs one entry per label file")
+    return [int(r) for r in sample_rates]
+
+
+def _read_marks(path: str, rate):
+    """(marks, None) of a label file, or (None, the exception) where it is missing or unreadable."""
+    from . import labels as LB
+    try:
+        if isinstance(rate, Exception):
+            raise rate
+        if rate < 1:
+            raise ValueError(f"sample rate {rate} of {path}")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"no label file {path}")
+        return LB.marks_from_table(LB.read_labels(path)), None
+    except Exception as exc:
+        return None, exc
+
+
+def revise_from_labels(label_paths: Sequence[str], sample_rates=None, params: Dict = None,
+                       output_directory: str = None, gap_sec: float = 5.0, suffix: str = "_corrected",
+                       overwrite: bool = False, device: int = 0, wav_paths: Sequence[str] = None,
+                       mode: str = None) -> List[dict]:
+    """The analysis of a person's own marks: every corrected
+    ``<base>_labels.csv`` goes through ``Detector.marks_device``,
+    ``metrics_device`` and ``labels_device``, so the BPM curve, the HRV table,
+    HRR, slopes, inclines and declines, the summary, the ``Average BPM`` column
+    and the S1-S2 group statistics follow the corrected beats.  The times are
+    restated on the sample grid of the decimated rate (``labels.rows_from_marks``).
+
+    ``sample_rates``: the decimated rate the label times refer to, an int for
+    all files or one per file; or ``wav_paths``, from whose headers it is
+    worked out as the analysis does (``mode_design`` with `params` and `mode`).
+    Files are grouped by rate; a missing or unreadable label file is that
+    file's ``error``.
+
+    Returns one dict per file: ``final_peaks``, ``bpm_times``, ``bpm``,
+    ``final_metrics`` (as ``Metrics.to_host`` gives it; None with fewer than
+    two S1 marks), ``labels``, ``marks_record`` (bpmx_marks_record's counts)
+    and ``sr``.  With ``output_directory`` it writes
+    ``<base><suffix>_Analysis_Summary.md``, ``<base><suffix>_bpm_plot.csv``
+    and ``<base><suffix>_labels.csv`` (``written``: the paths), where <base> is
+    the label file's name without ``_labels.csv``; an existing file is left as
+    it is unless `overwrite` (``skipped``: those paths)."""
+    from . import beats as B
+    from . import labels as LB
+    from . import reports as R
+    params = dict(DEFAULT_PARAMS if params is None else params)
+    if mode is None:
+        mode = params.get("bpmx_mode", "reference")
+    n = len(label_paths)
+    rates = _label_rates(n, sample_rates, wav_paths, params, mode)
+    out: List[dict] = [None] * n
+    groups: Dict[int, List[int]] = {}
+    marks = [None] * n
+    for k, path in enumerate(label_paths):
+        marks[k], err = _read_marks(path, rates[k])
+        if err is not None:
+            out[k] = {"error": err}
+            continue
+        groups.setdefault(rates[k], []).append(k)
+    det = default_detector(device)
+    torch = __import__("torch")
+    for sr, idx in groups.items():
+        with det.lock, torch.cuda.stream(det.host_stream()):
+            beats = det.marks_device([marks[k] for k in idx], sr, params)
+            res = det.metrics_device(beats, params).to_host()
+            labs = det.labels_device(beats, gap_sec).to_host()
+            det.host_stream().synchronize()
+        for k, r, lab in zip(idx, res, labs):
+            r = dict(r, labels=lab, sr=sr)
+            out[k] = r
+            if output_directory is None:
+                continue
+            name = os.path.basename(label_paths[k])
+            base = (name[:-len("_labels.csv")] if name.endswith("_labels.csv") else os.path.splitext(name)[0]) + suffix
+            r["written"], r["skipped"] = [], []
+            m = r["final_metrics"]
+            if m is None:
+                continue
+            jobs = ((f"{base}_Analysis_Summary.md", lambda p: _write_text(p, R.summary_text(base, m))),
+                    (f"{base}_bpm_plot.csv", lambda p: B.write_bpm_csv(p, m)),
+                    (f"{base}_labels.csv", lambda p: lab is not None and LB.write_labels(p, lab, overwrite=True)))
+            for fname, write in jobs:
+                p = os.path.join(output_directory, fname)
+                if os.path.exists(p) and not overwrite:
+                    r["skipped"].append(p)
+                elif write(p):
+                    r["written"].append(p)
+    return out
+
+
+def _write_text(path: str, text: str) -> bool:
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(text)
+    return True
+
+
+def score_label_files(label_paths: Sequence[str], ref_label_paths: Sequence[str], sample_rates=None,
+                      tol_sec: float = 0.05, gap_sec: float = 5.0, device: int = 0,
+                      params: Dict = None) -> List[dict]:
+    """One person's labels scored against another's (inter-rater agreement):
+    the files of `label_paths` go through ``Detector.marks_device`` and
+    ``labels_device``, which restates them as the analysis' own label rows,
+    the files of `ref_label_paths` through ``upload_marks``, both into the
+    unchanged ``score_device``.  ``sample_rates``: the decimated rate, an int
+    or one per pair.  Returns per pair ``labels.score_summary``'s dict with
+    ``record`` and ``status``, or ``error`` where either file is missing or
+    unreadable."""
+    from . import labels as LB
+    params = dict(DEFAULT_PARAMS if params is None else params)
+    n = len(label_paths)
+    if len(ref_label_paths) != n:
+        raise ValueError("ref_label_paths needs one entry per label file")
+    LB.score_ms(tol_sec, gap_sec)
+    rates = _label_rates(n, sample_rates, None, params, "reference")
+    out: List[dict] = [None] * n
+    groups: Dict[int, List[int]] = {}
+    marks, refs = [None] * n, [None] * n
+    for k in range(n):
+        marks[k], err = _read_marks(label_paths[k], rates[k])
+        if err is None:
+            refs[k], err = _read_marks(ref_label_paths[k], rates[k])
+        if err is not None:
+            out[k] = {"error": err}
+            continue
+        groups.setdefault(rates[k], []).append(k)
+    det = default_detector(device)
+    torch = __import__("torch")
+    for sr, idx in groups.items():
+        with det.lock, torch.cuda.stream(det.host_stream()):
+            labs = det.labels_device(det.marks_device([marks[k] for k in idx], sr, params), gap_sec)
+            sc = det.score_device(labs, det.upload_marks([refs[k] for k in idx]), tol_sec, gap_sec, rows=False)
+            rec, st = sc.download()
+            det.host_stream().synchronize()
+        for j, k in enumerate(idx):
+            out[k] = dict(LB.score_summary(rec[j]), record=rec[j].copy(), status=int(st[j]))
+    return out
+
+
 def patch_reference(module) -> None:
     """Rebind an imported reference ``bpm_analysis`` module's hot path to the GPU.
 

@@ -300,6 +300,8 @@ class Beats:
     trace: Optional[Trace] = None  # beats_device(trace=True)
     params: Optional[dict] = None  # the parameter dict of the launch (the trace's strings quote thresholds)
     hints: "object" = None         # device [F] per-file hints the launch reads (kept alive with its results)
+    marks: "object" = None         # marks_device: the Marks the launch read
+    marks_record: "object" = None  # marks_device: device [F * N.MARKS_RECORD] int32, the counts per recording
 
     def to_host(self, explain: bool = False) -> List[dict]:
         """Per-file dicts as ``_host.beats`` returns them (final_peaks,
@@ -309,7 +311,10 @@ class Beats:
         ``skipped=True`` with its flags.  Two rounds of copies like
         ``Packed.to_host``: offsets, counts, status and pass values first, then
         the used prefix of each array.  Raises BpmxError (E_LIMIT) when the
-        peak table was too small.
+        peak table was too small.  A result of ``marks_device`` gives the same
+        dicts (``start_bpm`` NaN, no peak and recovery time) plus ``marks_record``,
+        the counts of bpmx_marks_record; a recording with fewer than two S1
+        marks (BPMX_MARKS_FEW) has empty ``final_peaks`` and curve.
 
         ``explain`` (needs ``beats_device(trace=True)`` with the parameter
         dict): the trace comes down in the same two rounds and every
@@ -325,7 +330,7 @@ class Beats:
         with det.lock:
             st = torch.cuda.current_stream(det.device)
             small = {"pk_off": pk.pk_off, "flags": pk.flags, "b_n_final": self.n_final, "b_n_bpm": self.n_bpm,
-                     "b_status": self.status, "b_pass": self.pass_}
+                     "b_status": self.status, "b_pass": self.pass_, "b_marks": self.marks_record}
             if explain:
                 small["t_n_lt"] = self.trace.n_lt
             pin = {k: det.staging(k, t.numel(), t.dtype) for k, t in small.items() if t is not None}
@@ -335,7 +340,7 @@ class Beats:
             meta = {k: h.numpy().copy() for k, h in pin.items()}
             pko = meta["pk_off"]
             tp = int(pko[F])
-            if tp > pk.cap_peaks or (meta["b_status"] == N.BEATS_OVERFLOW).any():
+            if tp > pk.cap_peaks or np.isin(meta["b_status"], (N.BEATS_OVERFLOW, N.MARKS_OVERFLOW)).any():
                 raise N.BpmxError(f"packed tables too small: {tp} peaks (capacity {pk.cap_peaks})", N.E_LIMIT)
             big = {"pk_idx": pk.pk_idx, "b_final": self.final_idx, "b_bpm_t": self.bpm_t, "b_bpm": self.bpm,
                    "b_tags": self.tags}
@@ -363,7 +368,7 @@ class Beats:
             r = {"raw_peaks": raw[a:a + n], "flags": int(flags[f])}
             if s == _host.E_FEW_PEAKS:
                 r["error"] = KeyError("dynamic_noise_floor_series")
-            elif s != _host.OK:
+            elif s != _host.OK and s != N.MARKS_FEW:
                 raise N.BpmxError(f"bpmx_beats_device: status {s} for recording {f}")
             else:
                 r.update(final_peaks=fin[a:a + nf], bpm_times=tab["b_bpm_t"][a:a + nb], bpm=tab["b_bpm"][a:a + nb],
@@ -378,6 +383,8 @@ class Beats:
                               dev=tab["t_dev"][a:a + n - 1])
                     r["trace"] = tr
                     r["analysis_data"] = X.assemble(r["raw_peaks"], int(pk.sr), self.params, tr)
+            if "b_marks" in meta:
+                r["marks_record"] = meta["b_marks"][f * N.MARKS_RECORD:(f + 1) * N.MARKS_RECORD]
             out.append(r)
         return out
 
@@ -1223,7 +1230,7 @@ class Detector:
 
     def set_options(self, options: int) -> None:
         """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL, N.OPT_LABELS_GLOBAL,
-        N.OPT_SCORE_GLOBAL; test/diagnostic)."""
+        N.OPT_SCORE_GLOBAL, N.OPT_MARKS_GLOBAL; test/diagnostic)."""
         with self.lock:
             N.check(self.L.bpmx_set_options(self.ctx, int(options)), "bpmx_set_options")
 
@@ -1373,6 +1380,65 @@ class Detector:
             N.check(self.L.bpmx_score_device(self.ctx, F, ctypes.byref(sp), ctypes.byref(k), ctypes.byref(lo),
                                              ctypes.byref(r), ctypes.byref(o), self.stream_handle()),
                     "bpmx_score_device")
+        return out
+
+    def marks_device(self, marks, sr: int, params: dict, nd: Optional[Sequence[int]] = None,
+                     cap_peaks: Optional[int] = None) -> Beats:
+        """bpmx_marks_device on the current stream: a person's corrected marks
+        (``upload_marks``' Marks, or the label tables it takes) as the peak
+        table, final beats and BPM curve of every recording at the decimated
+        rate `sr`, on the GPU, in the layouts ``metrics_device``,
+        ``labels_device`` and ``score_device`` consume (``labels.revise`` is the
+        same on the host).  ``params``: the parameter dict
+        (``output_smoothing_window_sec`` is read here; ``metrics_device`` reads
+        the rest).  ``nd``: the recordings' envelope lengths; a mark at or
+        beyond its recording's is dropped.  The result's ``packed`` holds the
+        rows (``pk_env`` / ``pk_floor`` NaN, no trough table), its ``trace``
+        the zero ``gap``, ``marks_record`` the counts.  ``cap_peaks`` defaults
+        to the number of marks, which always suffices.  Asynchronous."""
+        torch = _torch()
+        if not hasattr(self.L, "bpmx_marks_device"):
+            raise N.BpmxError("libbpmx.so has no bpmx_marks_device; rebuild")
+        if not isinstance(marks, Marks):
+            marks = self.upload_marks(marks)
+        F, dev = marks.n_files, self.device
+        if nd is not None and len(nd) != F:
+            raise N.BpmxError("marks_device: nd needs one entry per recording", N.E_ARG)
+        cap_ref = marks.cap_ref
+        cap = cap_ref if cap_peaks is None else int(cap_peaks)
+        n = max(cap, 1)
+        e = lambda k, dt: torch.empty(k, dtype=dt, device=dev)  # noqa: E731
+        doff = np.zeros(F + 1, dtype=np.int64)
+        d_nd = None
+        if nd is not None:
+            doff[1:] = np.cumsum(np.asarray(nd, dtype=np.int64))
+            d_nd = torch.from_numpy(np.asarray(nd, dtype=np.int64)).to(dev)
+        packed = Packed(det=self, sr=int(sr), doff=doff, cap_peaks=cap, cap_troughs=0, safe_peaks=cap_ref,
+                        safe_troughs=0, pk_off=e(F + 1, torch.int64), tr_off=None, pk_idx=e(n, torch.int32),
+                        pk_env=e(n, torch.float64), pk_floor=e(n, torch.float64), tr_idx=None, tr_env=None,
+                        y16=None, y_max=None)
+        out = Beats(det=self, packed=packed, final_idx=e(n, torch.int32), n_final=e(F, torch.int32),
+                    bpm_t=e(n, torch.float64), bpm=e(n, torch.float64), n_bpm=e(F, torch.int32),
+                    pass_=e(3 * F, torch.float64), tags=e(n, torch.int8), status=e(F, torch.int32),
+                    trace=Trace(record=None, code=None, lt_pos=None, lt_bpm=None, n_lt=None, dev_t=None, dev=None,
+                                gap=e(n, torch.int32)),
+                    params=dict(params), marks=marks, marks_record=e(F * N.MARKS_RECORD, torch.int32))
+        out.hints = d_nd                 # read by the launch: alive as long as its results
+        k = N.PackedOut()
+        k.cap_peaks = cap
+        k.pk_off, k.pk_idx = packed.pk_off.data_ptr(), packed.pk_idx.data_ptr()
+        k.pk_env, k.pk_floor = packed.pk_env.data_ptr(), packed.pk_floor.data_ptr()
+        o = N.BeatsOut()
+        o.final_idx, o.n_final = out.final_idx.data_ptr(), out.n_final.data_ptr()
+        o.bpm_t, o.bpm, o.n_bpm = out.bpm_t.data_ptr(), out.bpm.data_ptr(), out.n_bpm.data_ptr()
+        o.pass_, o.tags, o.status = out.pass_.data_ptr(), out.tags.data_ptr(), out.status.data_ptr()
+        r = N.RefMarks(cap_ref, marks.rf_off.data_ptr(), marks.rf_ms.data_ptr(), marks.rf_type.data_ptr())
+        mp = N.MarksParams(float(params["output_smoothing_window_sec"]))
+        with self.lock:
+            N.check(self.L.bpmx_marks_device(self.ctx, F, int(sr), ctypes.byref(mp), ctypes.byref(r),
+                                             None if d_nd is None else d_nd.data_ptr(), ctypes.byref(k),
+                                             ctypes.byref(o), out.trace.gap.data_ptr(), out.marks_record.data_ptr(),
+                                             self.stream_handle()), "bpmx_marks_device")
         return out
 
     def score_sweep(self, recordings: List[np.ndarray], fs: int, params_list: Sequence[dict],

@@ -43,6 +43,9 @@ A result ("labels") is a dict:
 The last part scores such a table against a person's corrected label file
 (``marks_from_table``, ``score``, ``score_summary``, ``score_csv_text``): the
 definition of ``Detector.score_device`` (bpmx_score_device) in plain Python.
+After it, ``rows_from_marks`` and ``revise`` turn a corrected table into beats
+and analyse those: the definition of ``Detector.marks_device``
+(bpmx_marks_device) and the host route behind it.
 """
 from __future__ import annotations
 
@@ -554,3 +557,73 @@ def score_csv_text(table: Optional[Dict], result: Dict) -> str:
             rows.append((t, 1, f"{repr(t)},{TYPE_NAME[int(marks['type'][i])]},FN,\n"))
     rows.sort(key=lambda r: (r[0], r[1]))
     return ",".join(SCORE_COLUMNS) + "\n" + "".join(r[2] for r in rows)
+
+
+# ---------------------------------------------------------------- corrected marks as beats
+# There is no reference implementation of the conversion: include/bpmx.h (bpmx_marks_device) is the definition,
+# csrc/bpmx_marks_core.h states it for host and device, and this is the same in numpy.
+MARKS_OK, MARKS_FEW, MARKS_OVERFLOW = 0, -24, -25                             # bpmx_marks_status
+MK_N_ROWS, MK_N_S1, MK_N_S2, MK_N_MERGED, MK_N_DROPPED, MK_N_OTHER, MARKS_RECORD = 0, 1, 2, 3, 4, 5, 8
+
+
+def rows_from_marks(marks: Optional[Dict], sr: int, nd: Optional[int] = None) -> Dict:
+    """The rows of a person's marks (``marks_from_table``'s dict, or a label
+    table, which goes through it; any dict with ``ms`` and ``type``) at the
+    decimated rate `sr`, integers only: a mark whose type is neither S1 nor
+    S2 is skipped, one with ``ms < 0``, ``idx = (ms * sr + 500) // 1000 >
+    INT32_MAX`` or (with `nd`) ``idx >= nd`` is dropped, a run of kept marks
+    on one sample becomes one row, S1 if any of them is.  Returns ``idx``
+    (int64), ``type`` (int8), ``final`` (the S1 rows' idx) and ``record``
+    (int32 [8]: rows, S1, S2, merged, dropped, other, 0, 0).  Times are
+    restated as ``round(idx / sr, 3)``: a time off the sample grid snaps to
+    the nearest sample."""
+    if marks is None or "ms" not in marks:
+        marks = marks_from_table(marks)
+    ms = np.asarray(marks["ms"]).astype(np.int64)
+    typ = np.asarray(marks["type"]).astype(np.int64)
+    typed = (typ == S1) | (typ == S2)
+    idx = (np.maximum(ms, 0) * int(sr) + 500) // 1000
+    ok = (ms >= 0) & (idx <= _I32[1])
+    if nd is not None:
+        ok &= idx < int(nd)
+    keep = typed & ok
+    ki, kt = idx[keep], typ[keep]
+    head = np.ones(len(ki), dtype=bool)
+    head[1:] = ki[1:] != ki[:-1]
+    starts = np.flatnonzero(head)
+    any_s1 = np.logical_or.reduceat(kt == S1, starts) if len(starts) else np.zeros(0, dtype=bool)
+    r_idx, r_type = ki[head], np.where(any_s1, S1, S2).astype(np.int8)
+    rec = np.zeros(MARKS_RECORD, dtype=np.int32)
+    rec[MK_N_ROWS], rec[MK_N_S1] = len(r_idx), int(any_s1.sum())
+    rec[MK_N_S2] = rec[MK_N_ROWS] - rec[MK_N_S1]
+    rec[MK_N_MERGED] = len(ki) - len(r_idx)
+    rec[MK_N_DROPPED] = int((typed & ~ok).sum())
+    rec[MK_N_OTHER] = int((~typed).sum())
+    return {"idx": r_idx.astype(np.int64), "type": r_type, "final": r_idx[r_type == S1].astype(np.int64), "record": rec}
+
+
+def revise(table_or_marks: Optional[Dict], sr: int, params: Dict, gap_sec: float = 5.0,
+           nd: Optional[int] = None) -> Dict:
+    """The analysis of a person's own marks on the host: ``rows_from_marks``,
+    ``beats.final_metrics`` on the S1 indices (curve, HRV table, HRR, slopes,
+    inclines and declines, summary) and ``from_curve`` on the rows, so the
+    label table's ``Average BPM`` and the group statistics follow the
+    corrected curve.  Returns ``rows``, ``record``, ``final_peaks``,
+    ``status`` (MARKS_OK, or MARKS_FEW with fewer than two S1 rows),
+    ``final_metrics`` and ``labels`` (both None with MARKS_FEW; ``labels``
+    also where the curve has no row; ``final_metrics`` also where scipy's
+    find_peaks rejects the curve's spacing, with the ValueError as ``error``,
+    as ``Metrics.to_host`` reports it)."""
+    from . import beats as B
+    rows = rows_from_marks(table_or_marks, sr, nd)
+    out = {"rows": rows, "record": rows["record"], "final_peaks": rows["final"], "status": MARKS_FEW,
+           "final_metrics": None, "labels": None}
+    if len(rows["final"]) >= 2:
+        out["status"] = MARKS_OK
+        try:
+            out["final_metrics"] = B.final_metrics(rows["final"], int(sr), params)
+        except ValueError as e:                       # scipy's, where the curve is too dense for find_peaks' distance
+            out["error"] = e
+        s, t = B.bpm_series(rows["final"], int(sr), params)
+        out["labels"] = from_curve(rows["idx"], rows["type"], int(sr), t, s.values, gap_sec) if len(s) else None
+    return out

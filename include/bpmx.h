@@ -54,7 +54,8 @@ extern "C" {
 
 /* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
  * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL;
- * bpmx_score_device and BPMX_OPT_SCORE_GLOBAL. */
+ * bpmx_score_device and BPMX_OPT_SCORE_GLOBAL; bpmx_marks_device and
+ * BPMX_OPT_MARKS_GLOBAL. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
@@ -169,7 +170,9 @@ enum bpmx_option {
                                         applies (test/diagnostic) */
     BPMX_OPT_SCORE_GLOBAL = 262144,  /* bpmx_score_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS (test/diagnostic) */
-    BPMX_OPT_LABELS_GLOBAL = 131072  /* bpmx_labels_device (set with bpmx_set_options): every recording's
+    BPMX_OPT_MARKS_GLOBAL = 524288,  /* bpmx_marks_device (set with bpmx_set_options): every recording's
+                                        workspace in global memory instead of LDS (test/diagnostic) */
+    BPMX_OPT_LABELS_GLOBAL = 131072 /* bpmx_labels_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS (test/diagnostic) */
 };
 
@@ -690,8 +693,85 @@ int bpmx_score_device(bpmx_ctx *ctx, int32_t n_files, const bpmx_score_params *p
                       const bpmx_labels_out *labels, const bpmx_ref_marks *ref, const bpmx_score_out *out,
                       void *stream);
 
+/* A person's corrected marks as beats on the device (bpmx_marks_device).
+ *
+ * The reference computes the BPM curve, the HRV table, HRR, slopes and the
+ * summary from nothing but the final S1 indices (_calculate_final_metrics,
+ * bpm_analysis.py:1701-1722).  This stage turns a table of a person's marks
+ * (bpmx_ref_marks, as for bpmx_score_device) into the peak-table and
+ * bpmx_beats_out layouts that bpmx_metrics_device, bpmx_labels_device and
+ * bpmx_score_device consume, so those run unchanged on the corrected beats.
+ * There is no reference implementation of the conversion; this is the
+ * definition (csrc/bpmx_marks_core.h states it for host and device,
+ * labels.rows_from_marks in Python).  Integers only, so both agree exactly.
+ *
+ *   Rows from marks, per recording, in table order:
+ *     - a mark whose type is neither S1 nor S2 is skipped (N_OTHER);
+ *     - a mark with ms < 0 is dropped (N_DROPPED);
+ *     - idx = (ms * sr + 500) / 1000 in int64; a mark with idx > INT32_MAX or,
+ *       with nd, idx >= nd[f] is dropped (N_DROPPED);
+ *     - a run of kept marks with equal idx becomes one row, S1 if any mark of
+ *       the run is S1, else S2; the removed marks are counted (N_MERGED).
+ *   With rf_ms ascending the rows are strictly ascending in idx, which is what
+ *   bpmx_labels_device requires of pk_idx.  N_ROWS + N_MERGED + N_DROPPED +
+ *   N_OTHER is the number of marks of the file.
+ *
+ *   Outputs, in the existing layouts (slices start at pk_off[f]):
+ *     pk_off[n_files + 1]: the exclusive prefix sums of the row counts, the
+ *         true totals even when they exceed cap_peaks (as bpmx_pack);
+ *     pk_idx: the rows' idx; pk_env / pk_floor (optional): quiet NaN;
+ *     tags: BPMX_TAG_S1 / BPMX_TAG_S2 per row; gap: 0 per row, so the labels
+ *         stage takes the type from the tag;
+ *     final_idx, n_final: the S1 rows' idx, ascending;
+ *     bpm_t, bpm, n_bpm: calculate_bpm_series of those (beats_series of
+ *         csrc/bpmx_beats_core.h, the text bpmx_beats_device runs) at
+ *         smoothing_window_sec (output_smoothing_window_sec);
+ *     pass (optional): NaN;
+ *     record: 8 int32 per file (bpmx_marks_record).
+ *
+ * The label times the later stages make are round(idx / sr, 3): the person's
+ * own millisecond for sr >= 1000, and any time the labeler or a label file of
+ * this project can hold for sr < 1000; a hand-typed time off the sample grid
+ * snaps to the nearest sample.  A recording never has more rows than marks:
+ * cap_peaks = cap_ref always suffices. */
+typedef struct {
+    double smoothing_window_sec;    /* > 0: output_smoothing_window_sec */
+} bpmx_marks_params;
+
+enum bpmx_marks_status {        /* bpmx_beats_out.status as bpmx_marks_device writes it, beside BPMX_HOST_OK */
+    BPMX_MARKS_FEW = -24,       /* fewer than two S1 rows: n_final and n_bpm are 0; rows, tags, gap and the record
+                                   are still written (the later stages then answer *_NONE) */
+    BPMX_MARKS_OVERFLOW = -25   /* a slice reaches past cap_peaks or cap_ref, or rf_off descends: nothing written
+                                   but the status */
+};
+
+enum bpmx_marks_record {        /* record: 8 int32 per file */
+    BPMX_MK_N_ROWS = 0, BPMX_MK_N_S1 = 1, BPMX_MK_N_S2 = 2,
+    BPMX_MK_N_MERGED = 3,       /* marks removed because they fell on the sample of the mark before them */
+    BPMX_MK_N_DROPPED = 4,      /* ms < 0, idx > INT32_MAX or idx >= nd[f] */
+    BPMX_MK_N_OTHER = 5,        /* a type that is neither S1 nor S2 */
+    BPMX_MARKS_RECORD = 8       /* 6 and 7 are reserved zeros */
+};
+
+/* The marks of n_files recordings at decimated rate sr as rows, beats and
+ * curve, asynchronously on `stream`.  marks: rf_off and cap_ref < 2^31 (with
+ * cap_ref > 0, rf_ms and rf_type).  nd: optional device [n_files], the
+ * recordings' envelope lengths.  tables (out): cap_peaks < 2^31, pk_off and
+ * pk_idx required, pk_env / pk_floor optional, the rest ignored.  beats (out):
+ * final_idx, n_final, bpm_t, bpm, n_bpm, tags and status required, pass
+ * optional.  gap [cap_peaks] and record [n_files][BPMX_MARKS_RECORD] are
+ * required.  Nothing outside a file's used entries is written, and nothing is
+ * read or written beyond cap_ref and cap_peaks.  Never synchronises the host;
+ * scratch comes from ctx.  n_files = 0 does nothing.  Three launches: rows per
+ * recording, the scan of the counts, beats and curve per recording; see
+ * csrc/k_marks.hip. */
+int bpmx_marks_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_marks_params *params,
+                      const bpmx_ref_marks *marks, const int64_t *nd, const bpmx_packed *tables,
+                      const bpmx_beats_out *beats, int32_t *gap, int32_t *record, void *stream);
+
 /* bpmx_option bits for the entry points that take no bpmx_params
- * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL, BPMX_OPT_SCORE_GLOBAL);
+ * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL, BPMX_OPT_SCORE_GLOBAL,
+ * BPMX_OPT_MARKS_GLOBAL);
  * they hold until set again. */
 int bpmx_set_options(bpmx_ctx *ctx, int32_t options);
 
