@@ -2,7 +2,9 @@
  * bpmx_plan.h — which kernels a run takes and how they are sized, as pure host
  * arithmetic over the run's parameters and the batch's shape: no HIP runtime
  * call, no context, no allocation.  bpmx_run.hip sequences the launches over
- * these plans; tests/plan_driver.hip prints them without a GPU.
+ * these plans; tests/plan_driver.hip prints them without a GPU.  The native
+ * envelope's block-kernel plan is bpmx_native_plan.h, which
+ * k_envelope_native.hip includes with the kernels it sizes.
  */
 #ifndef BPMX_PLAN_H
 #define BPMX_PLAN_H

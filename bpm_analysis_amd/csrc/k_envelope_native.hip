@@ -40,6 +40,7 @@
 #include "bpmx_common.h"
 #include "bpmx_kernels.h"
 #include "bpmx_native.h"
+#include "bpmx_native_plan.h"
 #include "bpmx_hilbert.h"
 #ifndef BPMX_NM_POLICY
 #define BPMX_NM_POLICY " nt"   /* cache policy of the metric block kernel's PCM stream: non-temporal (r05 A/B: the kernel -1.8 %, k_native_yd +0.006 ms; "" = default) */
@@ -60,7 +61,6 @@ enum { TB_A = 0, TB_V = 0, TB_B = 16, TB_C = 20, TB_D = 24, TB_M = 25, TB_P = 41
  * blocks [[a, b], [-b, a]] — in its first 24 doubles; TT_VI = V^-1 */
 enum { TT_KPOW = 0, TT_MT = 96, TT_G0 = 112, TT_ALPHA = 128, TT_BETA = 384, TT_VI = 640, TT_SIZE = 656 };
 constexpr int NAT_PART = 16;          /* doubles per partial-tile block record: u4 v4 x pad3 S4 */
-constexpr int NAT_DSMAX = 1280;       /* decimation factors up to fs/300 - 1 at 384 kHz (tail buffers) */
 
 struct NatTile {
     int64_t s0;                         /* first frame of the tile (index into pcm frames) */
@@ -105,12 +105,7 @@ struct NatCarryArgs {
     InitOutArgs io;                /* io.flags non-null: reset recording f's outputs first */
     const double *ttab;            /* tail tables (NAT_TT_ROWS rows of 16): C A^m | A^m B | A^m zi | h_m */
 };
-/* k_native_carry's tail recursion, lane-parallel: the exact per-sample
- * recursion z' = A z + B u, y = C z + D u (SosStep, original basis) over the
- * nt <= NAT_TT_PAR tail samples as its impulse response, row m of the tail
- * table holding C A^m, A^m B, A^m zi and h_m (h_0 = D, h_m = C A^(m-1) B),
- * built on the host in long double from the same coefficients */
-constexpr int NAT_TT_ROWS = NAT_DSMAX + 20, NAT_TT_PAR = 320;
+/* the tail tables' geometry (NAT_TT_ROWS, NAT_TT_PAR): bpmx_native_plan.h */
 
 struct NatYdArgs {
     const NatTile *tiles;
@@ -266,6 +261,7 @@ __device__ __forceinline__ double dot4(const V4 &a, const V4 &b) {
  * here would sit behind the next tile's prefetch in vmcnt order and stall the
  * wave until the whole prefetch landed. */
 enum { ET_KPOW = 0, ET_P = 24, ET_C = 40, ET_D = 44, ET_SIZE = 45 };
+static_assert(ET_SIZE == NAT_ET_SIZE, "bpmx_native_plan.h sizes the LDS-DMA kernel's LDS with it");
 __device__ __forceinline__ void nat_stage_epilogue_tables(const NatBlockArgs &A, double *et) {
     for (int i = threadIdx.x; i < ET_SIZE; i += blockDim.x) {
         double v;
@@ -328,8 +324,8 @@ __device__ __forceinline__ void nat_tile_epilogue(const NatBlockArgs &A, const d
  * HBM latency hides behind the current tile's FMAs — then go through LDS,
  * where lane b reads block b's ds+1 samples (lane stride ds/2 dwords: odd for
  * the usual ds, conflict-free).  The 8 coefficients of each sample are
- * wave-uniform scalar loads. */
-constexpr int NB_RCH = 20;              /* 16-byte chunks per lane per tile: <= 10240 samples */
+ * wave-uniform scalar loads.  NB_RCH 16-byte chunks per lane per tile
+ * (bpmx_native_plan.h). */
 
 __device__ __forceinline__ double nat_lo16(uint32_t w) { return (double)(int)(int16_t)(w & 0xFFFFu); }
 __device__ __forceinline__ double nat_hi16(uint32_t w) { return (double)((int)w >> 16); }
@@ -520,14 +516,8 @@ constexpr int NM_WAVES = 4;
 #endif
 constexpr int NM_SLOTS = BPMX_NM_SLOTS;             /* LDS tile slots per wave */
 constexpr int NM_MINW = 2;                        /* waves per SIMD the register budget must allow */
-constexpr int NM_NDMA = 18;                      /* DMA wave-instructions per tile, always all issued, all lanes on */
-constexpr int NM_SLOT_CH = NM_NDMA * 64;          /* 16-byte chunks per slot (18,432 B) */
-
-/* blocks per tile the slot holds: every k of the last block's K steps (+2
- * samples for the odd-offset align) must stay inside the slot */
-__host__ __device__ constexpr int nm_tile_blocks(int ds, int ks) {
-    return ((NM_SLOT_CH * 8 - 7 - 32 * ks - 2) / ds + 1) < 64 ? ((NM_SLOT_CH * 8 - 7 - 32 * ks - 2) / ds + 1) : 64;
-}
+/* NM_NDMA DMA wave-instructions per tile, NM_SLOT_CH chunks per slot and the
+ * blocks a slot holds (nm_tile_blocks): bpmx_native_plan.h */
 
 template <int KS>
 __global__ __launch_bounds__(64 * NM_WAVES, NM_MINW) void k_native_blocks_mfma(NatBlockArgs A, const nm_i4 *__restrict__ afrag,
@@ -717,12 +707,8 @@ template __global__ void k_native_blocks_mfma<5>(NatBlockArgs, const nm_i4 *, co
  * runs once per 64 blocks with every lane busy.  Step s + 1's LDS words are
  * requested before step s's products issue (one wave per SIMD: nothing else
  * hides the LDS latency). */
-constexpr int NB_WAVES = 4, NB_SLOTS = 2, NB_NDMA = 19;   /* waves, slots per wave, DMA instructions (KiB) per slot */
-__host__ __device__ inline int nb_sub_blocks(int ds, int ch, int ks64, int ndma) {
-    const int hw = ndma * 64 * 8;                    /* halfwords per slot */
-    const int b = (hw - 7 - 64 * ks64 - 2) / (ds * ch) + 1;
-    return b < 16 ? b : 16;                          /* one 16-column N tile per sub-tile */
-}
+/* NB_WAVES, NB_SLOTS, NB_NDMA and the blocks per sub-tile (nb_sub_blocks):
+ * bpmx_native_plan.h */
 template <int N>
 __device__ __forceinline__ void nb_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 /* wait until at most k sub-tiles' DMA (k * NDMA instructions) are outstanding */
@@ -929,25 +915,8 @@ template __global__ void k_native_blocks_mfma_big<10, NB_SLOTS, NB_NDMA, NB_WAVE
  * and halved at the end — every partial sum differs by an exact factor of 2,
  * so this equals accumulating c_i * ((L_i + R_i) / 2), the f64 mean the
  * reference forms (bpm_analysis.py:1016). */
-constexpr int ND_WAVES = 4;
-constexpr int ND_LDS = 160 * 1024;
-
-/* host: DMA wave-instructions per tile (1 KiB each) so that four slots, the
- * coefficient table and the epilogue constants fit the CU's LDS */
-inline int nd_ndma(int ds) {
-    const int coef = (ds + 1) * 64;
-    const int n = (ND_LDS - coef - 1024) / (ND_WAVES * 1024);
-    return n < 38 ? n : 38;
-}
-/* blocks per tile: the slot holds the <= 7-element alignment offset and
- * (bt ds + 1) frames of ch int16 elements; at most 32 (two lanes per block) */
-inline int nd_tile_blocks(int ds, int ch) {
-    const int n = nd_ndma(ds);
-    if (n < 1) return 0;
-    const int b = ((n * 64 * 8 - 7) / ch - 1) / ds;
-    return b < 32 ? b : 32;
-}
-inline size_t nd_lds_bytes(int ds) { return (size_t)nd_ndma(ds) * ND_WAVES * 1024 + (size_t)(ds + 1) * 64 + ET_SIZE * 8; }
+/* ND_WAVES and the slot sizing (nd_ndma, nd_tile_blocks, nd_lds_bytes):
+ * bpmx_native_plan.h */
 
 template <int CH>
 __global__ __launch_bounds__(64 * ND_WAVES, 1) void k_native_blocks_dma(NatBlockArgs A, int ndma) {
@@ -1082,7 +1051,6 @@ __device__ __forceinline__ Cx2 shfl_down_cx2(const Cx2 &x, int d) {
     return Cx2{__shfl_down(x.a1, d), __shfl_down(x.b1, d), __shfl_down(x.a2, d), __shfl_down(x.b2, d)};
 }
 
-constexpr int NAT_CPF = 8;      /* tiles per lane held in registers by k_native_carry */
 __global__ __launch_bounds__(64) void k_native_carry(NatCarryArgs A, SosStep SS) {
     const int f = blockIdx.x;
     if (f >= A.n_files) return;
@@ -1937,39 +1905,25 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
     const int64_t *d_foff = G.d_foff, *d_doff = G.d_doff;
     const int32_t *d_active = G.d_active;
     const int ds = P->ds;
-    if (ds > NAT_DSMAX) return fail(BPMX_E_LIMIT, "native mode supports ds <= " + std::to_string(NAT_DSMAX));
+    /* the block kernel and its tile length (bpmx_native_plan.h) */
+    NativePlan np;
+    if (native_block_plan(P->dtype, P->channels, ds, P->options, (unsigned)((uintptr_t)B->pcm & 15),
+                          foff[F] * P->channels, &np) != BPMX_OK)
+        return fail(BPMX_E_LIMIT, "native mode supports ds <= " + std::to_string(NAT_DSMAX));
     int rc = BPMX_OK;
-    /* tables (cached on the host key; uploaded when they change) */
     /* tables and block offsets: rebuilt / re-uploaded only when they change (the
      * host copies live in the context, so the async upload never outlives them) */
-    /* tiles of bt blocks: the int16 path's LDS tile holds <= NB_RCH*512 samples */
-    /* matrix-core path: int16 mono, ds + 1 <= 160 (KS K steps of 32 samples) */
-    const int mfma_ks = ds + 1 <= 96 ? 3 : (ds + 1 <= 160 ? 5 : 0);
-    const bool aligned16 = ((uintptr_t)B->pcm & 15) == 0;
-    const bool i16_fast = P->dtype == BPMX_DT_I16 && aligned16 && foff[F] * P->channels >= 16 &&
-                          !(P->options & (BPMX_OPT_NATIVE_F64 | BPMX_OPT_NATIVE_DMA));
-    const bool use_mfma = mfma_ks && i16_fast && P->channels == 1;
-    /* int16 mono beyond K = 160 and int16 stereo: the big-K matrix-core kernel
-     * (K = channels x (ds + 1) <= 640, K steps of 64) */
-    const int kbig = P->channels * (ds + 1);
-    const int big_ks = kbig <= 320 ? 5 : (kbig <= 640 ? 10 : 0);
-    const int big_bs = big_ks ? nb_sub_blocks(ds, P->channels, big_ks, NB_NDMA) : 0;
-    const bool use_big = !use_mfma && i16_fast && big_ks && (P->channels == 1 || P->channels == 2) && big_bs >= 1;
-    /* the rest of int16 stereo (and, on request, mono) through the LDS-DMA f64 kernel */
-    const bool use_dma = !use_mfma && !use_big && P->dtype == BPMX_DT_I16 && aligned16 && foff[F] * P->channels >= 16 &&
-                         (P->channels == 2 || (P->channels == 1 && (P->options & BPMX_OPT_NATIVE_DMA))) &&
-                         !(P->options & BPMX_OPT_NATIVE_F64) && nd_tile_blocks(ds, P->channels) >= 1;
-    /* tiles of bt blocks: the LDS tile (slot) must hold the tile's samples */
-    const int bt = use_mfma ? nm_tile_blocks(ds, mfma_ks)
-                 : use_big  ? big_bs * (64 / big_bs)
-                 : (use_dma ? nd_tile_blocks(ds, P->channels) : std::min(64, (NB_RCH * 512 - 16) / ds));
+    const int mfma_ks = np.mfma_ks, big_ks = np.big_ks, big_bs = np.big_bs, bt = np.bt;
+    const bool use_mfma = np.route == NAT_R_MFMA3 || np.route == NAT_R_MFMA5;
+    const bool use_big = np.route == NAT_R_BIG5 || np.route == NAT_R_BIG10;
+    const bool use_dma = np.route == NAT_R_DMA1 || np.route == NAT_R_DMA2;
     std::vector<int64_t> key(17);
     for (int i = 0; i < 12; ++i) std::memcpy(&key[i], &P->sos[i], 8);
     key[12] = ds;
     std::memcpy(&key[13], &P->sos_zi[0], 8);
     std::memcpy(&key[14], &P->sos_zi[2], 8);
-    key[15] = bt;
-    key[16] = use_big ? 1000 * P->channels + big_ks : 0;
+    key[15] = np.key15;
+    key[16] = np.key16;
     size_t mfma_off = 0;                                     /* in doubles, into nat_tab */
     if (key != ctx->nat_key) {
         std::vector<LD> cl((size_t)(ds + 1) * 8);
@@ -1999,7 +1953,7 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
     const double *d_tt = d_tab + TB_COEF + 8 * (size_t)(ds + 1);
     mfma_off = TB_COEF + 8 * (size_t)(ds + 1) + TT_SIZE;
     /* geometry: block offsets, per-file tile offsets, the tile list (cached with the context) */
-    const int64_t gstr = (bt + 15) / 16 * 16;                 /* gamma row per tile */
+    const int64_t gstr = np.gstr;                             /* gamma row per tile */
     std::vector<int64_t> tk(4 + 2 * (F + 1));
     tk[0] = bt; tk[1] = F; tk[2] = ds; tk[3] = 0;
     for (int f = 0; f <= F; ++f) { tk[4 + f] = foff[f]; tk[5 + F + f] = doff[f]; }
@@ -2049,7 +2003,7 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
         NatBlockArgs a;
         a.pcm = B->pcm; a.tiles = d_tiles; a.n_tiles = nt; a.total = foff[F]; a.bt = bt;
         a.channels = P->channels; a.ds = ds; a.tab = d_tab; a.tt = d_tt; a.gam = gam; a.agg = agg; a.part = part;
-        const bool fast = P->dtype == BPMX_DT_I16 && P->channels == 1 && ((uintptr_t)B->pcm & 15) == 0;
+        const bool fast = np.route == NAT_R_I16;
         const unsigned grid = (unsigned)std::min<int64_t>(nt, 256 * 8);
         if (use_mfma) {
             const double *mt = d_tab + mfma_off;
@@ -2070,7 +2024,7 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
             const double *mt = d_tab + mfma_off;
             const nm_i4 *init = (const nm_i4 *)(mt + 8), *af = (const nm_i4 *)(mt + 8 + 32);
             const unsigned g1 = (unsigned)std::min<int64_t>((nt + NB_WAVES - 1) / NB_WAVES, 256);
-            const size_t lds = (size_t)NB_SLOTS * NB_NDMA * NB_WAVES * 1024;
+            const size_t lds = np.lds;
             if (big_ks == 5) {
                 (void)hipFuncSetAttribute((const void *)k_native_blocks_mfma_big<5, NB_SLOTS, NB_NDMA, NB_WAVES>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2085,8 +2039,8 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
         } else if (use_dma) {
             a.total = foff[F] * P->channels;                 /* int16 elements */
             const unsigned g1 = (unsigned)std::min<int64_t>((nt + ND_WAVES - 1) / ND_WAVES, 256);
-            const int ndma = nd_ndma(ds);
-            const size_t lds = nd_lds_bytes(ds);
+            const int ndma = np.ndma;
+            const size_t lds = np.lds;
             if (P->channels == 2) {
                 (void)hipFuncSetAttribute((const void *)k_native_blocks_dma<2>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

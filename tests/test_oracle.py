@@ -285,3 +285,37 @@ def test_oracle_under_sanitizers(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
     assert r.returncode == 0, r.stderr[-2000:]
     assert "SANITIZE OK" in r.stdout
+
+
+@pytest.mark.parametrize("ch", [1, 2, 3])
+@pytest.mark.parametrize("dtype", ["u8", "i16", "i32", "f32", "f64"])
+def test_native_y_is_scipys_in_every_sample_format(dtype, ch):
+    """preprocess_native's decimated signal is scipy.signal.sosfiltfilt of the
+    same-dtype array (np.mean over the channels first, as the reference
+    forms it), decimated, bit for bit: the int16 goldens pin the oracle for
+    int16 only, and odd_ext's arithmetic in the array's dtype (wrap-around for
+    mono integers, float32 rounding, neither for a float64 mean) differs per
+    format.  Recordings with tests/native_cases.py's edges, on which that
+    arithmetic decides the result: asserted through the same samples cast to
+    float64 first."""
+    from scipy.signal import sosfiltfilt
+    from tests import native_cases as NC
+    ds = 146
+    fs = NC.rate(ds)
+    d = O.derive(fs, NC.params(ds))
+    assert (d.ds, d.sr, d.env_w) == (ds, 320, 32)
+    for i, n in enumerate((15 * ds + 1, 16 * ds, 41 * ds + 73)):
+        x = NC.recording(dtype, ch, n, fs, 4100 + i)
+        assert x.dtype == NC.NP_DT[dtype] and x.shape == ((n,) if ch == 1 else (n, ch))
+        env, y = O.preprocess_native(x, d, return_y=True)
+        work = x if ch == 1 else np.mean(x, axis=1)
+        assert work.dtype == (x.dtype if ch == 1 or dtype == "f32" else np.float64)
+        want = sosfiltfilt(d.sos, work)[::ds]
+        assert y.dtype == want.dtype == np.float64 and np.array_equal(y, want), (n, dtype, ch)
+        dist = NC.discrimination(y, NC.cast_y(x, d))
+        if dtype == "f64" or (ch > 1 and dtype != "f32"):
+            assert dist == 0.0                                  # no wrap, no rounding: the cast changes nothing
+        elif dtype == "f32":
+            assert dist > 0.0
+        else:
+            assert dist >= 1e-3, dist
