@@ -42,7 +42,9 @@ OPT_RECT_SEQ = 65536               # rectified mode: the pandas recursion for ev
 OPT_LABELS_GLOBAL = 131072          # bpmx_labels_device, through bpmx_set_options (test/diagnostic)
 OPT_SCORE_GLOBAL = 262144           # bpmx_score_device, through bpmx_set_options (test/diagnostic)
 OPT_MARKS_GLOBAL = 524288           # bpmx_marks_device, through bpmx_set_options (test/diagnostic)
+OPT_FLOOR_ONEWG = 1048576           # the floor by one workgroup per recording, not two halves (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
+STAT_FLOOR_WHOLE = 3                # recordings the half-recording floor launch handed to the whole-recording one
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
 BEATS_SKIPPED, BEATS_OVERFLOW = -16, -17      # bpmx_beats_out.status, beside _host.OK / _host.E_FEW_PEAKS
 # bpmx_metrics_out.status: 0, the two bits, or a negative code

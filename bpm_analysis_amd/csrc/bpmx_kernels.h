@@ -459,7 +459,7 @@ struct WmLayout {
 constexpr int WM_NBK = WM_MMAX / 64 + 2;
 constexpr int WM_META_LOW = (WM_NBK * 22 + 7) & ~7;
 constexpr int WM_META_B = WM_META_LOW + WM_NBK * 22;
-__host__ __device__ inline size_t wm_align16(size_t x) { return (x + 15) & ~(size_t)15; }
+__host__ __device__ constexpr inline size_t wm_align16(size_t x) { return (x + 15) & ~(size_t)15; }
 __host__ __device__ inline WmLayout wm_layout(int64_t nmax, bool prune) {
     const int64_t n = nmax < 1 ? 1 : (nmax > WM_MMAX ? WM_MMAX : nmax);
     const int64_t m = prune && n > WM_PMAX ? WM_PMAX : n;
@@ -484,6 +484,53 @@ __host__ __device__ inline WmLayout wm_layout(int64_t nmax, bool prune) {
 template <bool PRUNE>
 __global__ void k_rollq_wm_t(RollqArgs A, uint16_t *pos_scratch, int32_t *full);
 __global__ void k_floor_wm(FloorWmArgs A);
+
+/* k_floor_wm_half: the final floor by two 512-thread workgroups per recording,
+ * (f, c) making outputs [c h, min(n, (c + 1) h)), h = wmh_split(n), over the
+ * samples those windows reach (the chunk mode of the pruned body).  Its LDS
+ * is sized so that two workgroups share a CU: at most WMH_MMAX samples in
+ * reach (a 60 s recording's half at the default 10 s window) and WMH_PMAX
+ * kept ones.  What a half cannot finish exactly it flags in redo[f], and
+ * k_floor_wm recomputes those recordings whole in a second launch. */
+constexpr int WMH_T = 512;
+constexpr int WMH_MMAX = 10752;              /* samples a half's windows reach: 168 position blocks */
+constexpr int WMH_PMAX = 4224;               /* kept samples of a half: 28 % above the largest half of the bench's
+                                                recordings, seeds 0..1023 (tools/prune_sim.py halves) */
+constexpr int WMH_TRMAX = 448;               /* troughs a half stages */
+constexpr int WMH_NBK = WMH_MMAX / 64 + 2;
+constexpr int WMH_META_LOW = (WMH_NBK * 22 + 7) & ~7;
+constexpr int WMH_META_B = WMH_META_LOW + WMH_NBK * 22;
+constexpr size_t WMH_LDS_MAX = 79 * 1024;    /* dynamic + static, so that two fit in a CU's 160 KiB */
+__host__ __device__ inline int64_t wmh_split(int64_t n) { return (((n + 1) >> 1) + 63) & ~(int64_t)63; }
+/* samples the windows of the larger half of an n-sample recording reach */
+__host__ __device__ inline int64_t wmh_reach(int64_t n, int64_t W) {
+    const int64_t h = wmh_split(n), off = (W - 1) / 2;
+    const int64_t r0 = h + off < n ? h + off : n;            /* half 0: [0, h - 1 + 1 + off) */
+    const int64_t s1 = h + 1 + off - W > 0 ? h + 1 + off - W : 0;
+    return r0 > n - s1 ? r0 : n - s1;
+}
+/* a recording the split launch takes by length and window (else it is flagged
+ * up front: at n <= 2 W + 128 a half reaches the whole recording) */
+__host__ __device__ inline bool wmh_eligible(int64_t n, int64_t W) {
+    return n > 2 * W + 128 && n <= WM_MMAX && wmh_reach(n, W) <= WMH_MMAX;
+}
+/* the half's layout: the per-64 tables by WMH_NBK, the phase area the sort of
+ * WMH_PMAX kept samples with its counters and per-wave digit bins */
+__host__ __device__ constexpr inline WmLayout wmh_layout() {
+    const int64_t NWV = WMH_T / 64;
+    const int64_t sort_b = 8 * (int64_t)WMH_PMAX + NWV * 128 * 4 + NWV * 256 * 8;
+    const int64_t hist_b = (int64_t)WMH_NBK * 64 * 2 + NWV * 64 * 4 + WMH_MMAX;
+    WmLayout l{};
+    l.tab = 0;
+    l.meta = wm_align16((size_t)WMH_TRMAX * 20 + (size_t)WMH_NBK * 4);
+    l.kpos = wm_align16(l.meta + (size_t)WMH_META_B);
+    l.area = wm_align16(l.kpos + (size_t)WMH_PMAX * 2);
+    l.total = l.area + (size_t)(sort_b > hist_b ? sort_b : hist_b);
+    return l;
+}
+static_assert(wmh_layout().total + 1024 <= WMH_LDS_MAX, "k_floor_wm_half: dynamic LDS plus 1 KB of static");
+__global__ void k_floor_wm_half(FloorWmArgs A, int32_t *redo);
+__global__ void k_count_flags(const int32_t *flag, int n, int64_t *out);
 
 /* bpmx_pack (k_pack.hip): table w = 0 is the raw peaks', 1 the troughs' */
 enum { PK_SCAN_T = 1024, PK_GATHER_T = 128, PK_Y16_T = 256 };

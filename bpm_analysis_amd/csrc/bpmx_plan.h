@@ -53,6 +53,14 @@ struct DetectPlan {
     /* recordings of <= WM_MMAX samples: everything after the draft bracket
      * in one launch (k_floor_wm), the static floor's quantile included */
     bool floor_wm;
+    /* ... its final rolling quantile by two half-recording workgroups per
+     * recording that share a CU (k_floor_wm_half), then k_floor_wm over the
+     * recordings they hand back: when the longest recording is eligible by
+     * length (shorter ones are handed back one by one), unless
+     * BPMX_OPT_FLOOR_ONEWG; the run also asks the context whether two of the
+     * workgroups are resident per CU */
+    bool floor_split;
+    size_t wmh_lds;
     /* rolling-quantile geometry: T outputs per step, sorted union in LDS */
     int64_t W;
     int cap;
@@ -123,6 +131,8 @@ inline int detect_plan(const bpmx_params &P, int F, int64_t maxnd, bool ordered,
     D.wm_n = std::min<int64_t>(maxnd, WM_MMAX);
     D.wm_lds_p = wm_layout(D.wm_n, true).total;
     D.wm_lds = wm_layout(D.wm_n, false).total;
+    D.floor_split = D.floor_wm && !(P.options & BPMX_OPT_FLOOR_ONEWG) && wmh_eligible(maxnd, W);
+    D.wmh_lds = wmh_layout().total;
     D.wm_c = (WM_MMAX - W + 1) / 64 * 64;
     D.wm_chunks = D.use_wm && maxnd > WM_MMAX && !(P.options & BPMX_OPT_ROLLQ_NOPRUNE) && D.wm_c >= 2048;
     D.wm_nch = D.wm_chunks ? (maxnd + D.wm_c - 1) / D.wm_c : 1;

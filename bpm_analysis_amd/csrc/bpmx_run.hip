@@ -78,6 +78,29 @@ void wm_lds_attr(int device) {
     done[(size_t)device] = 1;
 }
 
+/* whether two k_floor_wm_half workgroups are resident per CU, asked once per
+ * device (the current one) with its dynamic-LDS limit raised; when the
+ * runtime answers anything else the split launch has no point and the run
+ * takes k_floor_wm alone */
+bool wmh_two_resident(int device) {
+    static std::mutex mu;
+    static std::vector<signed char> ans;
+    std::lock_guard<std::mutex> lk(mu);
+    if (device < 0) return false;
+    if ((int)ans.size() <= device) ans.resize((size_t)device + 1, -1);
+    if (ans[(size_t)device] < 0) {
+        const size_t lds = wmh_layout().total;
+        int nb = 0;
+        const bool ok =
+            hipFuncSetAttribute((const void *)k_floor_wm_half, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) ==
+                hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_floor_wm_half, WMH_T, lds) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        ans[(size_t)device] = ok && nb == 2 ? 1 : 0;
+    }
+    return ans[(size_t)device] == 1;
+}
+
 /* one run's state, handed from stage to stage */
 struct Run {
     bpmx_ctx *ctx;
@@ -112,6 +135,7 @@ struct Run {
     double *rawv, *trv, *dense, *draft;
     uint16_t *wm_pos, *wm_pos_ch;      /* wavelet matrix: rank -> index, per recording and per chunk */
     int32_t *wm_full, *wm_fail;
+    int32_t *wm_redo;                  /* [F] recordings k_floor_wm_half hands to k_floor_wm */
 };
 
 int check_args(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const bpmx_out *O) {
@@ -733,6 +757,7 @@ int floor_buffers(Run &R) {
     if (D.use_wm) {
         R.wm_pos = (uint16_t *)ctx->buf("wm_pos", (size_t)sumnd * 2, &rc);
         R.wm_full = (int32_t *)ctx->buf("wm_full", (size_t)F * 4, &rc);
+        if (D.floor_split) R.wm_redo = (int32_t *)ctx->buf("wm_redo", (size_t)F * 4, &rc);
     }
     if (D.wm_chunks) {
         R.wm_fail = (int32_t *)ctx->buf("wm_fail", (size_t)F * 4, &rc);
@@ -787,6 +812,19 @@ int floor_stage(Run &R) {
         if (R.noise_lazy) a.qn = noise_level(R);
         a.floor = O->floor; a.draft = R.draft; a.an_draft = G.d_an1; a.an_final = G.d_an2; a.full = R.wm_full;
         wm_lds_attr(ctx->device);
+        if (D.floor_split && wmh_two_resident(ctx->device)) {
+            /* two half-recording workgroups per recording, then the whole-
+             * recording kernel over what they handed back: it exits at once
+             * for the others and is the last writer of the rest */
+            HIP_TRY(hipMemsetAsync(R.wm_redo, 0, (size_t)F * 4, s));
+            LAUNCH(ctx, s, "k_floor_wm", k_floor_wm_half, dim3(F, 2), dim3(WMH_T), D.wmh_lds, s, a, R.wm_redo);
+            if (R.d_stats)
+                LAUNCH(ctx, s, "k_count_flags", k_count_flags, dim3(1), dim3(256), 0, s, R.wm_redo, F,
+                       R.d_stats + BPMX_STAT_FLOOR_WHOLE);
+            a.sa.active = R.wm_redo;
+            LAUNCH(ctx, s, "k_floor_wm[whole]", k_floor_wm, dim3(F), dim3(WM_T), std::max(D.wm_lds_p, D.wm_lds), s, a);
+            return BPMX_OK;
+        }
         LAUNCH(ctx, s, "k_floor_wm", k_floor_wm, dim3(F), dim3(WM_T), std::max(D.wm_lds_p, D.wm_lds), s, a);
         return BPMX_OK;
     }

@@ -42,6 +42,8 @@
  *      of a wavelet matrix over the rank sequence; building its levels and the
  *      descents cost more than the whole of this phase.)
  * Recordings longer than WM_MMAX decimated samples take k_rolling_quantile.
+ * k_floor_wm_half (end of this file) runs the same phases as two 512-thread
+ * workgroups per recording, half of the outputs each, two resident per CU.
  */
 #include "bpmx_common.h"
 #include "bpmx_kernels.h"
@@ -77,33 +79,48 @@ struct RqShared {
     double vmin, vmax;
 };
 
-template <bool PRUNE>
+/* T threads.  HALF (k_floor_wm_half, T = WMH_T, PRUNE): chunk mode over the two
+ * halves of a recording of at most WM_MMAX samples, blockIdx.y = half, with the
+ * half's own layout and caps; a half that cannot finish sets wm_fail[f], and a
+ * finished one fills its own NaN prefix and suffix. */
+template <bool PRUNE, int T = WM_T, bool HALF = false>
 __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch, int32_t *full, RqShared &S_) {
-    constexpr int NWV = WM_T / 64;
-    constexpr int MMAX = PRUNE ? WM_PMAX : WM_MMAX;          /* samples in the structure */
-    constexpr int MAXIT = MMAX / WM_T;
+    static_assert(!HALF || PRUNE, "the half mode is the pruned body's chunk mode");
+    constexpr int NWV = T / 64;
+    constexpr int PMAX = HALF ? WMH_PMAX : WM_PMAX;          /* kept samples of the pruned variant */
+    constexpr int MMAX = PRUNE ? PMAX : WM_MMAX;             /* samples in the structure */
+    constexpr int MAXIT = (MMAX + T - 1) / T;
+    constexpr int TRMAX = HALF ? WMH_TRMAX : WM_TRMAX;       /* troughs staged */
+    constexpr int RMAX = HALF ? WMH_MMAX : WM_MMAX;          /* samples in reach */
+    constexpr int NBK = RMAX / 64 + 2;                       /* entries of the per-64 tables */
+    constexpr int META_LOW = HALF ? WMH_META_LOW : WM_META_LOW;
     const int f = blockIdx.x;
     if (f >= A.n_files) return false;
     const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
     if (!A.run[f]) {
-        if (PRUNE && tid == 0) full[f] = 0;
+        if (PRUNE && !HALF && tid == 0) full[f] = 0;
         return false;
     }
     const int64_t d0 = A.doff[f], n = A.doff[f + 1] - d0;
     const int ntr_all = A.env ? A.ntr[f] : 0;
     /* chunk mode: a long recording's outputs [o0, o1) in workgroup (f, chunk),
      * over the samples [t0, top) their windows reach */
-    const bool chunked = PRUNE && A.wm_chunk > 0 && n > WM_MMAX && A.env;
+    const bool chunked = HALF || (PRUNE && A.wm_chunk > 0 && n > WM_MMAX && A.env);
     if (!chunked && blockIdx.y > 0) return false;
     const int64_t W = A.window, minp = A.min_periods;
     int64_t o0 = 0, o1 = n, t0 = 0, top = n;
     int jlo = 0, ntr = ntr_all;                              /* troughs staged: [jlo, jlo + ntr) */
     int &s_jlo = S_.jlo, &s_jhi = S_.jhi;
     if (chunked) {
-        if (tid == 0 && blockIdx.y == 0) full[f] = 0;        /* long: never the unpruned variant */
-        o0 = (int64_t)blockIdx.y * A.wm_chunk;
-        if (o0 >= n) return false;
-        o1 = min<int64_t>(n, o0 + A.wm_chunk);
+        if (!HALF && tid == 0 && blockIdx.y == 0) full[f] = 0;   /* long: never the unpruned variant */
+        if (HALF) {
+            o0 = (int64_t)blockIdx.y * wmh_split(n);
+            o1 = min<int64_t>(n, o0 + wmh_split(n));
+        } else {
+            o0 = (int64_t)blockIdx.y * A.wm_chunk;
+            if (o0 >= n) return false;
+            o1 = min<int64_t>(n, o0 + A.wm_chunk);
+        }
         int64_t s, e;
         win_bounds(o0, n, W, s, e);
         const int64_t *tr = A.troughs + d0;
@@ -121,16 +138,20 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         __syncthreads();
         jlo = s_jlo;
         ntr = s_jhi - s_jlo + 1;
-        if (top <= t0) {                                     /* no finite sample in reach: NaN outputs */
-            for (int64_t i = o0 + tid; i < o1; i += WM_T) A.out[d0 + i] = __builtin_nan("");
+        if (HALF && top <= t0) {                             /* no valid output of its own */
+            if (tid == 0) A.wm_fail[f] = 1;
             return false;
         }
-        if (top - t0 > WM_MMAX || ntr > WM_TRMAX) {
+        if (top <= t0) {                                     /* no finite sample in reach: NaN outputs */
+            for (int64_t i = o0 + tid; i < o1; i += T) A.out[d0 + i] = __builtin_nan("");
+            return false;
+        }
+        if (top - t0 > RMAX || ntr > TRMAX) {
             if (tid == 0) A.wm_fail[f] = 1;
             return false;
         }
     }
-    const bool fused = A.env && ntr <= WM_TRMAX;
+    const bool fused = A.env && ntr <= TRMAX;
     if (!chunked && (n > WM_MMAX || n <= 0 || (PRUNE && !fused))) {   /* k_rolling_quantile / the unpruned variant */
         if (PRUNE && tid == 0) full[f] = (n <= WM_MMAX && n > 0) ? 1 : 0;
         return PRUNE && n <= WM_MMAX && n > 0;
@@ -145,33 +166,33 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
     (void)pos_scratch;
     if (!chunked) t0 = A.troughs[d0];
     const int mall = (int)(top - t0);                        /* finite samples dense[t0:top) */
-    const WmLayout Lay = wm_layout(chunked ? top - t0 : n, PRUNE);
+    const WmLayout Lay = HALF ? wmh_layout() : wm_layout(chunked ? top - t0 : n, PRUNE);
     if (tid == 0) { s_first = INT_MAX; s_last = -1; }
     STAMP_DECL
 
     /* dense = np.interp of the troughs (k_interp), evaluated here from env at
-     * the troughs staged in LDS when there are <= WM_TRMAX of them */
+     * the troughs staged in LDS when there are <= TRMAX of them */
     double *s_tv = (double *)(smem + Lay.tab);
-    double *s_sl = s_tv + WM_TRMAX;                          /* per-segment slope (pruned variant) */
-    int32_t *s_tp = (int32_t *)(s_sl + (PRUNE ? WM_TRMAX : 0));
-    int32_t *s_bj = s_tp + WM_TRMAX;                         /* [(top - xb)/64 + 1]: last trough <= block start */
+    double *s_sl = s_tv + TRMAX;                          /* per-segment slope (pruned variant) */
+    int32_t *s_tp = (int32_t *)(s_sl + (PRUNE ? TRMAX : 0));
+    int32_t *s_bj = s_tp + TRMAX;                         /* [(top - xb)/64 + 1]: last trough <= block start */
     const int64_t xb = chunked ? t0 : 0;                     /* block table origin */
     if (fused) {
         const int64_t *tr = A.troughs + d0 + jlo;
         const double *trv = A.tv + d0 + jlo;                 /* env at the troughs, beside them */
-        for (int j = tid; j < ntr; j += WM_T) {
+        for (int j = tid; j < ntr; j += T) {
             s_tp[j] = (int32_t)tr[j];
             s_tv[j] = trv[j];
         }
         __syncthreads();
-        for (int64_t b = tid; b <= ((top - xb) >> 6); b += WM_T) {
+        for (int64_t b = tid; b <= ((top - xb) >> 6); b += T) {
             int lo = 0, hi = ntr;
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_tp[mid] <= xb + (b << 6)) lo = mid + 1; else hi = mid; }
             s_bj[b] = lo - 1;
         }
         if (PRUNE) {
             /* the same slope interp_at computes, once per segment */
-            for (int j = tid; j + 1 < ntr; j += WM_T)
+            for (int j = tid; j + 1 < ntr; j += T)
                 s_sl[j] = (s_tv[j + 1] - s_tv[j]) / ((double)s_tp[j + 1] - (double)s_tp[j]);
         }
         __syncthreads();
@@ -180,7 +201,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
      * table (a staged run that stops before the recording's last trough always
      * reaches past every position asked for) */
     auto dval = [&](int64_t x) -> double {
-        if (!fused) {                                        /* > WM_TRMAX troughs: np.interp from global memory */
+        if (!fused) {                                        /* > TRMAX troughs: np.interp from global memory */
             if (!A.env) return dense[x];
             const int64_t *trg = A.troughs + d0;
             return interp_at(x, trg, [&](int j) { return A.tv[d0 + j]; }, ntr_all);
@@ -206,14 +227,14 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
     /* ---------------- 0. pruning (PRUNE only) ---------------- */
     const int NPB = (mall + 63) >> 6;                        /* 64-sample position blocks of dense[t0:n) */
     uint64_t *kmask = (uint64_t *)(smem + Lay.meta);         /* [NPB + 1] kept bits */
-    int32_t *kpre = (int32_t *)(kmask + (WM_MMAX / 64 + 2)); /* [NPB + 1] kept before the block */
-    uint8_t *thr = (uint8_t *)(kpre + (WM_MMAX / 64 + 2));   /* [NPB] highest bin kept */
-    uint8_t *bstar = thr + (WM_MMAX / 64 + 2);               /* [9][n/64] per output block, then sparse-table maxima */
+    int32_t *kpre = (int32_t *)(kmask + NBK); /* [NPB + 1] kept before the block */
+    uint8_t *thr = (uint8_t *)(kpre + NBK);   /* [NPB] highest bin kept */
+    uint8_t *bstar = thr + NBK;               /* [9][n/64] per output block, then sparse-table maxima */
     /* the lower side: samples below every reachable window's k-th smallest */
-    uint64_t *lmask = (uint64_t *)(smem + Lay.meta + WM_META_LOW);         /* [NPB + 1] low bits */
-    int32_t *lpre = (int32_t *)(lmask + (WM_MMAX / 64 + 2)); /* [NPB + 1] low samples before the block */
-    uint8_t *lthr = (uint8_t *)(lpre + (WM_MMAX / 64 + 2));  /* [NPB] lowest bin kept */
-    uint8_t *astar = lthr + (WM_MMAX / 64 + 2);              /* [9][n/64] per output block, then sparse-table minima */
+    uint64_t *lmask = (uint64_t *)(smem + Lay.meta + META_LOW);         /* [NPB + 1] low bits */
+    int32_t *lpre = (int32_t *)(lmask + NBK); /* [NPB + 1] low samples before the block */
+    uint8_t *lthr = (uint8_t *)(lpre + NBK);  /* [NPB] lowest bin kept */
+    uint8_t *astar = lthr + NBK;              /* [9][n/64] per output block, then sparse-table minima */
     uint16_t *kpos = (uint16_t *)(smem + Lay.kpos);          /* kept index -> position - t0 */
     int m = mall;
     if (PRUNE) {
@@ -223,7 +244,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
          * stays between segment ends up to rounding; the bins clamp) */
         {
             double lo = __builtin_inf(), hi = -__builtin_inf();
-            for (int j = tid; j < ntr; j += WM_T) { lo = fmin(lo, s_tv[j]); hi = fmax(hi, s_tv[j]); }
+            for (int j = tid; j < ntr; j += T) { lo = fmin(lo, s_tv[j]); hi = fmax(hi, s_tv[j]); }
             lo = wave_min(lo);
             hi = wave_max(hi);
             if (lane == 0) { s_or[wid] = (unsigned long long)__double_as_longlong(lo); s_and[wid] = (unsigned long long)__double_as_longlong(hi); }
@@ -238,8 +259,8 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
             }
         }
         uint16_t *hist = (uint16_t *)(smem + Lay.area);      /* [NPB + 1][NB], then the exclusive prefix over blocks */
-        int32_t *hsc = (int32_t *)(hist + (WM_MMAX / 64 + 2) * NB);   /* [NWV][NB] */
-        for (int j = tid; j < (NPB + 1) * NB / 2; j += WM_T) ((uint32_t *)hist)[j] = 0u;
+        int32_t *hsc = (int32_t *)(hist + NBK * NB);   /* [NWV][NB] */
+        for (int j = tid; j < (NPB + 1) * NB / 2; j += T) ((uint32_t *)hist)[j] = 0u;
         __syncthreads();
         const double vmin = s_vmin, span = s_vmax - s_vmin;
         const bool ok = span == span && span < __builtin_inf();
@@ -258,7 +279,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         uint8_t *bin8 = (uint8_t *)(hsc + NWV * NB);        /* [mall] bin of each sample */
         /* one 64-sample block per wave step: runs of equal bins (the curve is
          * piecewise monotone, so a block has few) each add their length */
-        for (int p0 = wid << 6; p0 < mall; p0 += WM_T) {
+        for (int p0 = wid << 6; p0 < mall; p0 += T) {
             const int p = p0 + lane, nv = min(64, mall - p0);
             const int b = p < mall ? vbin(dval(t0 + p)) : -1;
             if (p < mall) bin8[p] = (uint8_t)b;
@@ -274,7 +295,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         /* exclusive prefix over position blocks, per bin: 16 parts of rows */
         {
             const int b = tid & (NB - 1), g = tid >> 6;
-            constexpr int RPMAX = (WM_MMAX / 64 + 1 + NWV - 1) / NWV;
+            constexpr int RPMAX = (RMAX / 64 + 1 + NWV - 1) / NWV;
             const int rp = (NPB + NWV - 1) / NWV, r0 = g * rp, r1 = min(NPB, r0 + rp);
             int hv[RPMAX], sum = 0;
 #pragma unroll
@@ -309,7 +330,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
          * with >= k_max + 2 samples of the block's common window (full
          * position blocks only) at or below it, by binary search */
         const int NBO = (int)((o1 - o0 + 63) >> 6);
-        for (int B = tid; B < NBO; B += WM_T) {
+        for (int B = tid; B < NBO; B += T) {
             const int64_t ib = o0 + ((int64_t)B << 6), ie = min<int64_t>(o1, ib + 64) - 1;
             int64_t s0, e0, s1, e1;
             win_bounds(ib, n, W, s0, e0);
@@ -356,19 +377,19 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         __syncthreads();
         /* sparse table of b* maxima over 2^j consecutive blocks, j = 1 .. 8 */
         for (int j = 1; (1 << j) <= NBO; ++j) {
-            const uint8_t *src = bstar + (size_t)(j - 1) * (WM_MMAX / 64 + 2);
-            uint8_t *dst = bstar + (size_t)j * (WM_MMAX / 64 + 2);
-            for (int B = tid; B + (1 << j) <= NBO; B += WM_T) dst[B] = max(src[B], src[B + (1 << (j - 1))]);
-            const uint8_t *asrc = astar + (size_t)(j - 1) * (WM_MMAX / 64 + 2);
-            uint8_t *adst = astar + (size_t)j * (WM_MMAX / 64 + 2);
-            for (int B = tid; B + (1 << j) <= NBO; B += WM_T) adst[B] = min(asrc[B], asrc[B + (1 << (j - 1))]);
+            const uint8_t *src = bstar + (size_t)(j - 1) * NBK;
+            uint8_t *dst = bstar + (size_t)j * NBK;
+            for (int B = tid; B + (1 << j) <= NBO; B += T) dst[B] = max(src[B], src[B + (1 << (j - 1))]);
+            const uint8_t *asrc = astar + (size_t)(j - 1) * NBK;
+            uint8_t *adst = astar + (size_t)j * NBK;
+            for (int B = tid; B + (1 << j) <= NBO; B += T) adst[B] = min(asrc[B], asrc[B + (1 << (j - 1))]);
             __syncthreads();
         }
         STAMP(11);
         /* highest b* and lowest a* over the output blocks whose windows can
          * reach a position block */
         const int64_t off = (W - 1) / 2;
-        for (int pb = tid; pb < NPB; pb += WM_T) {
+        for (int pb = tid; pb < NPB; pb += T) {
             const int64_t a = t0 + ((int64_t)pb << 6);
             int64_t ilo = a - off > 0 ? a - off : 0;
             int64_t ihi = min<int64_t>(n - 1, a + 63 + W - off);
@@ -378,9 +399,9 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
             if (ihi < ilo) { thr[pb] = 0; lthr[pb] = NB; continue; }   /* no window here reaches it */
             const int B0 = (int)((ilo - o0) >> 6), B1 = (int)((ihi - o0) >> 6), len = B1 - B0 + 1;
             const int j = 31 - __clz(len);
-            const uint8_t *st = bstar + (size_t)j * (WM_MMAX / 64 + 2);
+            const uint8_t *st = bstar + (size_t)j * NBK;
             thr[pb] = max(st[B0], st[B1 - (1 << j) + 1]);
-            const uint8_t *sa = astar + (size_t)j * (WM_MMAX / 64 + 2);
+            const uint8_t *sa = astar + (size_t)j * NBK;
             lthr[pb] = min(sa[B0], sa[B1 - (1 << j) + 1]);
         }
         __syncthreads();
@@ -422,7 +443,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         __syncthreads();
         kc = s_mk;
         STAMP(13);
-        if (kc > WM_PMAX) {                                  /* too many kept: the unpruned variant */
+        if (kc > PMAX) {                                     /* too many kept: the unpruned variant */
             if (tid == 0) { if (chunked) A.wm_fail[f] = 1; else full[f] = 1; }
             return !chunked;
         }
@@ -457,7 +478,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
 
     /* LDS, sort phase: posA[m8] | posB[m8] | kh[m8] | cnt[NWV][128] (two 16-bit counters per word).
      * Slots >= m are padding: they sort last, so they are neither stored nor counted. */
-    const int IT = (m + WM_T - 1) / WM_T;                    /* rounds per wave */
+    const int IT = (m + T - 1) / T;                    /* rounds per wave */
     const int mu = __builtin_amdgcn_readfirstlane(m), ITu = __builtin_amdgcn_readfirstlane(IT);
     const int S = 64 * IT;                                   /* slots per wave */
     const int m8 = (m + 7) & ~7;
@@ -500,7 +521,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
             return shc ? (k > kbase ? k - kbase : 0ull) >> shc : k;
         };
         uint64_t kor = 0, kand = ~0ull;
-        for (int p = tid; p < m; p += WM_T) {
+        for (int p = tid; p < m; p += T) {
             posA[p] = (uint16_t)p;                           /* slot order == index order */
             const uint64_t k = ckey(p);
             kh[p] = (uint32_t)k;
@@ -513,7 +534,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         }
         if (lane == 0) { s_or[wid] = kor; s_and[wid] = kand; }
         if (wbin_all)
-            for (int j = tid; j < NWV * 256; j += WM_T) wbin_all[j] = 0ull;
+            for (int j = tid; j < NWV * 256; j += T) wbin_all[j] = 0ull;
         __syncthreads();
         uint64_t vary = 0;
         {
@@ -525,7 +546,7 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
         uint32_t *wc = cnt + wid * 128;
         for (int d = 0; d < 8; ++d) {
             if (d == 4 && (vary >> 32)) {                    /* high halves, indexed by index */
-                for (int p = tid; p < m; p += WM_T) kh[p] = (uint32_t)(ckey(p) >> 32);
+                for (int p = tid; p < m; p += T) kh[p] = (uint32_t)(ckey(p) >> 32);
                 __syncthreads();
             }
             if (((vary >> (8 * d)) & 0xFFull) == 0) continue;   /* uniform: constant digit, order unchanged */
@@ -624,13 +645,13 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
     }
     /* posA[r] = structure index of rank r; posB becomes its inverse */
     uint16_t *posR = posA, *rkx = posB;
-    for (int r = tid; r < m; r += WM_T) rkx[posR[r]] = (uint16_t)r;
+    for (int r = tid; r < m; r += T) rkx[posR[r]] = (uint16_t)r;
     if (svl)
-        for (int r = tid; r < m; r += WM_T) svl[r] = dval(t0 + spos(posR[r]));
+        for (int r = tid; r < m; r += T) svl[r] = dval(t0 + spos(posR[r]));
     __syncthreads();
     if (shc) {
         bool down = false;                                   /* a compact key hid an order */
-        for (int r = tid; r + 1 < m; r += WM_T) down |= svl[r] > svl[r + 1];
+        for (int r = tid; r + 1 < m; r += T) down |= svl[r] > svl[r + 1];
         if (__syncthreads_or(down)) {                        /* the full-width variant redoes it */
             if (tid == 0) { if (chunked) A.wm_fail[f] = 1; else full[f] = 1; }
             return !chunked;
@@ -911,6 +932,23 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
     if (threadIdx.x == 0 && A.stamps)
         for (int k = 0; k < 8; ++k) A.stamps[blockIdx.x * 16 + 8 + k] = dq[k];
 #endif
+    if (HALF) {
+        /* valid outputs are one run of the recording (nobs is unimodal): with
+         * a valid output in each half, the NaN outputs are a prefix of half 0
+         * and a suffix of half 1, filled from this half's own first / last valid
+         * output as .bfill().ffill() fills them.  A half without one leaves the
+         * recording to the whole-recording launch. */
+        const int first = s_first, last = s_last;
+        if (last < 0) {
+            if (tid == 0) A.wm_fail[f] = 1;
+            return false;
+        }
+        if (tid == 0 && blockIdx.y == 0) A.allnan[f] = 0;
+        const double vf = out[first], vl = out[last];
+        for (int64_t i = o0 + tid; i < first; i += T) out[i] = vf;
+        for (int64_t i = last + 1 + tid; i < o1; i += T) out[i] = vl;
+        return false;
+    }
     if (chunked) {                                           /* bfill / ffill over all chunks: k_rollq_fill */
         if (tid == 0 && s_last >= 0) {
             atomicMin(&A.vfirst[f], s_first);
@@ -926,8 +964,8 @@ __device__ __forceinline__ bool rollq_wm_body(RollqArgs A, uint16_t *pos_scratch
     }
     if (tid == 0) A.allnan[f] = 0;
     const double vf = out[first], vl = out[last];
-    for (int64_t i = tid; i < first; i += WM_T) out[i] = vf;
-    for (int64_t i = last + 1 + tid; i < n; i += WM_T) out[i] = vl;
+    for (int64_t i = tid; i < first; i += T) out[i] = vf;
+    for (int64_t i = last + 1 + tid; i < n; i += T) out[i] = vl;
     return false;
 }
 
@@ -1029,6 +1067,59 @@ __global__ __launch_bounds__(WM_T) void k_floor_wm(FloorWmArgs A) {
     if (fill || from_draft)
         for (int64_t i = tid; i < n; i += WM_T) floor[i] = from_draft ? draft[i] : v;
     if (tid == 0 && nanfb) A.sa.flags[f] |= BPMX_F_NAN_FLOOR;
+}
+
+/* ---------------------------------------------------------------------------
+ * k_floor_wm_half: k_floor_wm's final rolling quantile as two independent
+ * 512-thread workgroups per recording, grid (F, 2), in an LDS footprint that
+ * lets two of them share a CU: while one waits at a barrier of the pruning or
+ * the sort, or thins out at the end of the output phase, the other issues.
+ * Workgroup (f, c) makes outputs [c h, min(n, (c + 1) h)), h = wmh_split(n),
+ * from the samples those windows reach.  Both halves sanitise the recording:
+ * they store identical trough lists and read them back after their own
+ * barrier, so neither depends on the other's stores.  A recording that is not
+ * the common case is flagged in redo[f] (zeroed before the launch) and left
+ * to k_floor_wm, launched after this kernel over the flagged recordings:
+ * < 5 raw troughs, <= 2 or > WM_TRMAX sanitised ones, a length the halves do
+ * not take (wmh_eligible), and whatever the chunk body gives up (more than
+ * WMH_PMAX kept samples, a non-finite curve, a compact-key descent, a half
+ * with no valid output).
+ * ------------------------------------------------------------------------- */
+__global__ __launch_bounds__(WMH_T, 4) void k_floor_wm_half(FloorWmArgs A, int32_t *redo) {
+    __shared__ RqShared sh;
+    __shared__ int s_sc[WMH_T / 64 + 1];
+    const RollqArgs &R = A.rq;
+    const int f = blockIdx.x;
+    if (f >= R.n_files || !A.sa.active[f]) return;
+    const int64_t n = R.doff[f + 1] - R.doff[f];
+    const int m = A.sa.nraw[f], tid = threadIdx.x;
+    if (m < 5 || !wmh_eligible(n, R.window)) {               /* uniform: before any store */
+        if (tid == 0) redo[f] = 1;
+        return;
+    }
+    const int w = __builtin_amdgcn_readfirstlane(sanitize_wg<WMH_T>(A.sa, f, s_sc));   /* uniform */
+    __syncthreads();
+    if (w <= 2 || w > WM_TRMAX) {
+        if (tid == 0) redo[f] = 1;
+        return;
+    }
+    RollqArgs a = R;
+    a.troughs = A.sa.out;
+    a.tv = A.sa.outv;
+    a.ntr = A.sa.nout;
+    a.allnan = A.an_final;
+    a.out = A.floor;
+    a.run = A.sa.active;                                     /* (1 here) */
+    a.wm_fail = redo;
+    (void)rollq_wm_body<true, WMH_T, true>(a, nullptr, nullptr, sh);
+}
+
+/* out[0] += the number of set flags (BPMX_OPT_STATS) */
+__global__ __launch_bounds__(256) void k_count_flags(const int32_t *flag, int n, int64_t *out) {
+    int c = 0;
+    for (int i = threadIdx.x; i < n; i += 256) c += flag[i] != 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if (lane_id() == 0 && c) atomicAdd((unsigned long long *)out, (unsigned long long)c);
 }
 
 }  // namespace bpmx

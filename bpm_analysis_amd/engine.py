@@ -946,6 +946,18 @@ class Detector:
         return {"raw_troughs": int(buf[N.STAT_RAW_TROUGHS]), "undecided": int(buf[N.STAT_UNDECIDED]),
                 "full_draft_chunks": int(buf[N.STAT_FULL_DRAFT])}
 
+    def floor_whole(self) -> int:
+        """Recordings that the half-recording floor launch of the last run with
+        options | OPT_STATS handed to the whole-recording one
+        (BPMX_STAT_FLOOR_WHOLE).  Not among stats(): it depends on how the
+        batch was cut into runs (a pipelined run's chunk with no eligible
+        recording takes the one-workgroup launch and counts none)."""
+        buf = (ctypes.c_int64 * N.NSTATS)()
+        rc = self.L.bpmx_stats(self.ctx, buf, N.NSTATS)
+        if rc < 0:
+            N.check(rc, "bpmx_stats")
+        return int(buf[N.STAT_FLOOR_WHOLE])
+
     # ------------------------------------------------------------------ #
     def run_host(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                  stages: int = N.STAGE_ALL, want_y: bool = False, log: bool = False,

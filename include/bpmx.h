@@ -172,8 +172,12 @@ enum bpmx_option {
                                         workspace in global memory instead of LDS (test/diagnostic) */
     BPMX_OPT_MARKS_GLOBAL = 524288,  /* bpmx_marks_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS (test/diagnostic) */
-    BPMX_OPT_LABELS_GLOBAL = 131072 /* bpmx_labels_device (set with bpmx_set_options): every recording's
+    BPMX_OPT_LABELS_GLOBAL = 131072, /* bpmx_labels_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS (test/diagnostic) */
+    BPMX_OPT_FLOOR_ONEWG = 1048576   /* the floor after the draft by one 1024-thread workgroup per recording
+                                        (k_floor_wm alone) instead of two half-recording workgroups of 512
+                                        threads that share a compute unit, with k_floor_wm over the recordings
+                                        they hand back (test/diagnostic; the results are bit-identical) */
 };
 
 /* bpmx_stats counters of the last run with BPMX_OPT_STATS */
@@ -181,6 +185,7 @@ enum bpmx_stat {
     BPMX_STAT_RAW_TROUGHS = 0,   /* raw troughs of the recordings whose draft floor was bracketed */
     BPMX_STAT_UNDECIDED = 1,     /* of those, troughs the bracket left open: draft evaluated there exactly */
     BPMX_STAT_FULL_DRAFT = 2,    /* trough chunks whose recording fell back to the whole draft floor */
+    BPMX_STAT_FLOOR_WHOLE = 3,   /* recordings the half-recording floor launch handed to the whole-recording one */
     BPMX_NSTATS = 8
 };
 

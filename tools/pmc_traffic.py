@@ -57,6 +57,12 @@ def per_kernel(d: str, counter: str) -> dict:
         if cyc:                         # also per launch label, by position in the step's cycle
             by[cyc[seen[k] % len(cyc)]].append(sum(v))
             seen[k] += 1
+    # the split floor launch runs under the label k_floor_wm, and k_floor_wm itself
+    # (over the recordings the halves handed back) under k_floor_wm[whole]
+    if "k_floor_wm_half" in by:
+        if "k_floor_wm" in by:
+            by["k_floor_wm[whole]"] = by.pop("k_floor_wm")
+        by["k_floor_wm"] = by.pop("k_floor_wm_half")
     return {k: sum(v) / len(v) for k, v in by.items()}
 
 

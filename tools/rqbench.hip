@@ -1,9 +1,14 @@
 /*
  * rqbench.hip — phase timing of the final-floor rolling quantile
  * (k_rollq_wm_t<true>) on the bench's own inputs (tools/dump_floor_inputs.py),
- * checked bit for bit against the library's floor.
+ * checked bit for bit against the library's floor.  A second argument `half`
+ * runs the two half-recording workgroups of k_floor_wm_half instead (the same
+ * body, grid (F, 2) of 512 threads, two workgroups per CU): the phase cycles
+ * are then the sum over a recording's two halves, the per-wave times w0-w7
+ * half 0 and w8-w15 half 1, and the recordings a half hands back are counted
+ * and left out of the check.
  *   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DVARIANT...] tools/rqbench.hip -o tools/rqbench
- *   python tools/dump_floor_inputs.py 1024 native /tmp/floor_in.bin && ./tools/rqbench /tmp/floor_in.bin
+ *   python tools/dump_floor_inputs.py 1024 native /tmp/floor_in.bin && ./tools/rqbench /tmp/floor_in.bin [half]
  * Diagnostic builds: -DRQ_STOP_PRUNE / -DRQ_STOP_SORT end the kernel after
  * the pruning / the sort (phase costs by difference, e.g. with rocprofv3
  * --pmc SQ_INSTS_VALU; no output check), -DRQ_DIAG_Q prints per-block
@@ -15,13 +20,22 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 using namespace bpmx;
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
+/* the halves' body as k_floor_wm_half runs it; half c's stamps after half 0's */
+__global__ __launch_bounds__(WMH_T, 4) void k_rollq_half(RollqArgs A) {
+    __shared__ RqShared sh;
+    if (A.stamps) A.stamps += (size_t)blockIdx.y * A.n_files * 16;
+    (void)rollq_wm_body<true, WMH_T, true>(A, nullptr, nullptr, sh);
+}
+
 int main(int argc, char **argv) {
+    const bool half = argc > 2 && std::string(argv[2]) == "half";
     const char *path = argc > 1 ? argv[1] : "/tmp/floor_in.bin";
     FILE *fh = fopen(path, "rb");
     if (!fh) { printf("cannot open %s\n", path); return 1; }
@@ -55,7 +69,10 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&d_ntr, F * 4));
     CK(hipMalloc(&d_full, F * 4));
     CK(hipMalloc(&d_pos, N * 2));
-    CK(hipMalloc(&d_st, (size_t)F * 16 * 8));
+    CK(hipMalloc(&d_st, (size_t)F * 2 * 16 * 8));
+    int32_t *d_fail;
+    CK(hipMalloc(&d_fail, F * 4));
+    CK(hipMemset(d_fail, 0, F * 4));
     CK(hipMemcpy(d_env, env.data(), N * 8, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_doff, doff.data(), (F + 1) * 8, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_tr, tr.data(), N * 8, hipMemcpyHostToDevice));
@@ -64,7 +81,7 @@ int main(int argc, char **argv) {
     RollqArgs a;
     a.dense = nullptr; a.doff = d_doff; a.troughs = d_tr; a.run = d_run; a.n_files = F; a.window = 3020;
     a.min_periods = 3; a.cap = 0; a.q = 0.2; a.out = d_out; a.allnan = d_an; a.stamps = d_st;
-    a.wm_max = WM_MMAX; a.env = d_env; a.ntr = d_ntr; a.wm_chunk = 0; a.wm_fail = nullptr; a.wm_pos_ch = nullptr;
+    a.wm_max = WM_MMAX; a.env = d_env; a.ntr = d_ntr; a.wm_chunk = 0; a.wm_fail = d_fail; a.wm_pos_ch = nullptr;
     a.vfirst = a.vlast = nullptr;
     {   /* env at each trough, beside the troughs (the library's trough values) */
         std::vector<double> tvh(N, 0.0);
@@ -75,16 +92,27 @@ int main(int argc, char **argv) {
         CK(hipMemcpy(d_tv, tvh.data(), N * 8, hipMemcpyHostToDevice));
         a.tv = d_tv;
     }
-    const size_t lds = std::max(wm_layout(nd, true).total, wm_layout(nd, false).total);   /* the unpruned fallback runs in the same workgroup */
-    CK(hipFuncSetAttribute((const void *)k_rollq_wm_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = half ? wmh_layout().total
+                            : std::max(wm_layout(nd, true).total, wm_layout(nd, false).total);   /* the unpruned fallback runs in the same workgroup */
+    CK(hipFuncSetAttribute((const void *)k_rollq_wm_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                           (int)std::max(wm_layout(nd, true).total, wm_layout(nd, false).total)));
+    CK(hipFuncSetAttribute((const void *)k_rollq_half, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wmh_layout().total));
+    if (half) {
+        int nb = 0;
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_rollq_half, WMH_T, lds));
+        printf("k_rollq_half: %d workgroups resident per CU (lds %zu)\n", nb, lds);
+    }
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     float best = 1e9;
     for (int rep = 0; rep < 5; ++rep) {
-        CK(hipMemset(d_st, 0, (size_t)F * 16 * 8));
+        CK(hipMemset(d_st, 0, (size_t)F * 2 * 16 * 8));
         CK(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL(k_rollq_wm_t<true>, dim3(F), dim3(WM_T), lds, 0, a, d_pos, d_full);
+        if (half)
+            hipLaunchKernelGGL(k_rollq_half, dim3(F, 2), dim3(WMH_T), lds, 0, a);
+        else
+            hipLaunchKernelGGL(k_rollq_wm_t<true>, dim3(F), dim3(WM_T), lds, 0, a, d_pos, d_full);
         CK(hipGetLastError());
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
@@ -92,8 +120,17 @@ int main(int argc, char **argv) {
         CK(hipEventElapsedTime(&ms, e0, e1));
         best = ms < best ? ms : best;
     }
-    std::vector<unsigned long long> st((size_t)F * 16);
+    std::vector<unsigned long long> st((size_t)F * 16), st1((size_t)F * 16);
     CK(hipMemcpy(st.data(), d_st, st.size() * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(st1.data(), d_st + (size_t)F * 16, st1.size() * 8, hipMemcpyDeviceToHost));
+#ifdef RQ_DIAG_W
+    if (half)                                                /* w8-w15: half 1's eight waves */
+        for (int f = 0; f < F; ++f)
+            for (int k = 0; k < 8; ++k) st[(size_t)f * 16 + 8 + k] = st1[(size_t)f * 16 + k];
+#else
+    if (half)
+        for (size_t j = 0; j < st.size(); ++j) st[j] += st1[j];
+#endif
     double sum[16] = {0};
     for (int f = 0; f < F; ++f)
         for (int k = 0; k < 16; ++k) sum[k] += (double)st[(size_t)f * 16 + k];
@@ -133,11 +170,12 @@ int main(int argc, char **argv) {
     }
 #endif
     std::vector<int32_t> fl(F);
-    CK(hipMemcpy(fl.data(), d_full, F * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(fl.data(), half ? d_fail : d_full, F * 4, hipMemcpyDeviceToHost));
     int nfull = 0;
     for (int f = 0; f < F; ++f) nfull += fl[f];
-    printf("k_rollq_wm_t<1> F=%d nd=%ld lds=%zu: %.4f ms (best of 5); per-WG cycles %.0f; flagged full %d\n", F,
-           (long)nd, lds, best, tot / F, nfull);
+    printf("%s F=%d nd=%ld lds=%zu: %.4f ms (best of 5); per-%s cycles %.0f; flagged %s %d\n",
+           half ? "k_rollq_half" : "k_rollq_wm_t<1>", F, (long)nd, lds, best, half ? "recording (two WGs)" : "WG", tot / F,
+           half ? "for the whole-recording launch" : "full", nfull);
     for (int k = 0; k < 16; ++k)
         if (sum[k] > 0) printf("   %-10s %12.0f  %5.1f%%\n", names[k], sum[k] / F, 100.0 * sum[k] / tot);
 #if defined(RQ_STOP_PRUNE) || defined(RQ_STOP_SORT)
