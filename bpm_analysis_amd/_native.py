@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("BPMX_LIB") or os.path.join(_HERE, "libbpmx.so")
 ABI_VERSION = 4
 
 DT_U8, DT_I16, DT_I32, DT_F32, DT_F64 = 0, 1, 2, 3, 4
+DT_I24 = 5                          # packed 24-bit PCM: the int32 samples v << 8 (pcm24.Pcm24)
 MODE_REFERENCE, MODE_NATIVE, MODE_RECTIFIED = 0, 1, 2
 STAGE_ENVELOPE, STAGE_FLOOR, STAGE_PEAKS, STAGE_ALL = 1, 2, 4, 7
 F_STATIC_FLOOR, F_DRAFT_FLOOR, F_NAN_FLOOR, F_TOO_SHORT, F_BAD_WINDOW = 1, 2, 4, 8, 16

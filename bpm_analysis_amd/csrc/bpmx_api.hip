@@ -391,6 +391,7 @@ static size_t dtype_bytes(int dt) {
     switch (dt) {
     case BPMX_DT_U8: return 1;
     case BPMX_DT_I16: return 2;
+    case BPMX_DT_I24: return 3;
     case BPMX_DT_F64: return 8;
     default: return 4;
     }

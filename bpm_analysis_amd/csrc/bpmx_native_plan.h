@@ -48,6 +48,18 @@ BPMX_NP_HD constexpr int nm_tile_blocks(int ds, int ks) {
     return ((NM_SLOT_CH * 8 - 7 - 32 * ks - 2) / ds + 1) < 64 ? ((NM_SLOT_CH * 8 - 7 - 32 * ks - 2) / ds + 1) : 64;
 }
 
+/* k_native_blocks_mfma24: packed 24-bit mono in the same slots, as bytes.
+ * A tile's bytes start up to 15 past the slot's first (the DMA runs from the
+ * 16-byte boundary below them); the last block's last K step reads 13 dwords
+ * from the dword at or below its first byte, i.e. up to 3 * 32 ks + 4 bytes
+ * from the block's start.  Rounded down to an even count: k_hilbert_env makes
+ * yd of the full tiles itself only when a tile holds an even number of blocks */
+BPMX_NP_HD constexpr int nm24_tile_blocks(int ds, int ks) {
+    return ((NM_SLOT_CH * 16 - 15 - 96 * ks - 4) / (3 * ds) + 1) < 64
+               ? ((NM_SLOT_CH * 16 - 15 - 96 * ks - 4) / (3 * ds) + 1) & ~1
+               : 64;
+}
+
 /* k_native_blocks_mfma_big */
 constexpr int NB_WAVES = 4, NB_SLOTS = 2, NB_NDMA = 19;   /* waves, slots per wave, DMA instructions (KiB) per slot */
 BPMX_NP_HD inline int nb_sub_blocks(int ds, int ch, int ks64, int ndma) {
@@ -88,7 +100,9 @@ enum {
     NAT_R_DMA1,         /* k_native_blocks_dma<1>: int16 mono on request */
     NAT_R_DMA2,         /* k_native_blocks_dma<2>: the rest of int16 stereo */
     NAT_R_I16,          /* k_native_blocks_i16: int16 mono, f64 VALU */
-    NAT_R_GEN           /* k_native_blocks_gen<dtype, multi> */
+    NAT_R_GEN,          /* k_native_blocks_gen<dtype, multi> */
+    NAT_R_M24_3,        /* k_native_blocks_mfma24<3>: packed 24-bit mono, ds + 1 <= 96 */
+    NAT_R_M24_5         /* k_native_blocks_mfma24<5>: packed 24-bit mono, ds + 1 <= 160 */
 };
 
 struct NativePlan {
@@ -130,12 +144,20 @@ inline int native_block_plan(int dtype, int channels, int ds, int32_t options, u
                          (channels == 2 || (channels == 1 && (options & BPMX_OPT_NATIVE_DMA))) &&
                          !(options & BPMX_OPT_NATIVE_F64) && nd_tile_blocks(ds, channels) >= 1;
     const bool fast = dtype == BPMX_DT_I16 && channels == 1 && aligned16;
+    /* packed 24-bit mono on the matrix cores, at any byte alignment (its DMA
+     * starts at the 16-byte boundary below each tile); total >= 16: anything
+     * shorter holds no active recording and not always a whole 16-byte chunk */
+    const bool use_m24 = dtype == BPMX_DT_I24 && channels == 1 && N.mfma_ks && total >= 16 &&
+                         !(options & BPMX_OPT_NATIVE_F64);
     /* tiles of bt blocks: the LDS tile (slot) must hold the tile's samples;
      * the int16 path's LDS tile holds <= NB_RCH*512 samples */
     const int bt_gen = (NB_RCH * 512 - 16) / ds < 64 ? (NB_RCH * 512 - 16) / ds : 64;
     if (use_mfma) {
         N.route = N.mfma_ks == 3 ? NAT_R_MFMA3 : NAT_R_MFMA5;
         N.bt = nm_tile_blocks(ds, N.mfma_ks);
+    } else if (use_m24) {
+        N.route = N.mfma_ks == 3 ? NAT_R_M24_3 : NAT_R_M24_5;
+        N.bt = nm24_tile_blocks(ds, N.mfma_ks);
     } else if (use_big) {
         N.route = N.big_ks == 5 ? NAT_R_BIG5 : NAT_R_BIG10;
         N.bt = N.big_bs * (64 / N.big_bs);
@@ -151,13 +173,13 @@ inline int native_block_plan(int dtype, int channels, int ds, int32_t options, u
     } else {
         N.route = NAT_R_GEN;
         N.bt = bt_gen;
-        N.gen_dtype = dtype >= BPMX_DT_U8 && dtype <= BPMX_DT_F32 ? dtype : BPMX_DT_F64;
+        N.gen_dtype = (dtype >= BPMX_DT_U8 && dtype <= BPMX_DT_F32) || dtype == BPMX_DT_I24 ? dtype : BPMX_DT_F64;
         N.gen_multi = channels > 1;
         N.gen_staged = dtype == BPMX_DT_I16 && channels == 2 && (align & 3) == 0;
     }
     N.gstr = (N.bt + 15) / 16 * 16;
     N.key15 = N.bt;
-    N.key16 = use_big ? 1000 * channels + N.big_ks : 0;
+    N.key16 = use_big ? 1000 * channels + N.big_ks : (use_m24 ? 24 : 0);   /* the 24-bit tables differ from int16's */
     return BPMX_OK;
 }
 

@@ -243,9 +243,10 @@ inline RectPlan rect_plan(int dtype, int channels, int64_t w, int32_t options, i
     RectPlan R{};
     R.chunk = RECT_CHUNK;
     R.nch = std::max<int64_t>(1, (maxn + R.chunk - 1) / R.chunk);
-    R.integer = dtype <= BPMX_DT_I32 && channels <= 2 && w <= RECT_W_EXACT_MAX && !(options & BPMX_OPT_RECT_SEQ);
+    const bool wide = dtype == BPMX_DT_I32 || dtype == BPMX_DT_I24;          /* I24 is the int32 sample v << 8 */
+    R.integer = (dtype <= BPMX_DT_I32 || wide) && channels <= 2 && w <= RECT_W_EXACT_MAX && !(options & BPMX_OPT_RECT_SEQ);
     R.grid = dim3((unsigned)R.nch, (unsigned)F);
-    const size_t entry = dtype == BPMX_DT_I32 ? 8 : 4;       /* a workgroup's local prefix sums (k_rect.hip RPcm) */
+    const size_t entry = wide ? 8 : 4;       /* a workgroup's local prefix sums (k_rect.hip RPcm) */
     if (!R.integer) {
         R.route = RECT_GENERAL;
         const int64_t rows = (maxn + 63) / 64 * 64;

@@ -48,7 +48,7 @@ BPMX_HDI double rect_value(const void *pcm, int dtype, int channels, int64_t fra
     switch (work_dtype(dtype, channels)) {
     case BPMX_DT_U8: a = x; break;
     case BPMX_DT_I16:
-    case BPMX_DT_I32: a = (double)rect_abs_int(dtype, (int64_t)x); break;
+    case BPMX_DT_I32: a = (double)rect_abs_int(work_dtype(dtype, 1), (int64_t)x); break;
     case BPMX_DT_F32: a = (double)__builtin_fabsf((float)x); break;
     default: a = __builtin_fabs(x); break;
     }

@@ -143,7 +143,7 @@ int check_args(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, const b
     if (B->n_files < 1 || !B->frame_offsets) return fail(BPMX_E_ARG, "empty batch");
     if (P->mode != BPMX_MODE_REFERENCE && P->mode != BPMX_MODE_NATIVE && P->mode != BPMX_MODE_RECTIFIED)
         return fail(BPMX_E_ARG, "bad mode");
-    if (P->dtype < BPMX_DT_U8 || P->dtype > BPMX_DT_F64) return fail(BPMX_E_ARG, "bad dtype");
+    if (P->dtype < BPMX_DT_U8 || P->dtype > BPMX_DT_I24) return fail(BPMX_E_ARG, "bad dtype");
     if (P->channels < 1 || P->ds < 1 || P->sr < 1) return fail(BPMX_E_ARG, "bad channels/ds/sr");
     const int st = P->stages;
     if (st <= 0 || st > BPMX_STAGE_ALL) return fail(BPMX_E_ARG, "bad stage mask");
@@ -419,7 +419,8 @@ int envelope_ref(Run &R) {
     if (rc != BPMX_OK) return rc;
     const bool zb = P->ba_b[1] == 0.0 && P->ba_b[3] == 0.0 && P->ba_b[4] == P->ba_b[0] &&
                     P->ba_b[2] == -2.0 * P->ba_b[0] &&
-                    (P->dtype == BPMX_DT_U8 || P->dtype == BPMX_DT_I16 || P->dtype == BPMX_DT_I32);
+                    (P->dtype == BPMX_DT_U8 || P->dtype == BPMX_DT_I16 || P->dtype == BPMX_DT_I32 ||
+                     P->dtype == BPMX_DT_I24);
     /* without a side stream or its events: the unsplit form */
     const bool split = E.wants_split && ctx->side_ready() && ctx->ref_events((size_t)E.nfc);
     if (split) {
@@ -439,6 +440,10 @@ int envelope_ref(Run &R) {
     case BPMX_DT_I16: K = ref_kernels<BPMX_DT_I16>(multi, zb); break;
     case BPMX_DT_I32: K = ref_kernels<BPMX_DT_I32>(multi, zb); break;
     case BPMX_DT_F32: K = ref_kernels<BPMX_DT_F32>(multi, zb); break;
+    case BPMX_DT_I24:                              /* its own gather; the passes are int32's (same samples) */
+        K = ref_kernels<BPMX_DT_I32>(multi, zb);
+        K.pick = multi ? k_ref_pick<BPMX_DT_I24, true> : k_ref_pick<BPMX_DT_I24, false>;
+        break;
     default: K = ref_kernels<BPMX_DT_F64>(multi, zb); break;
     }
     if ((rc = ref_passes(R, E, split, K, a)) != BPMX_OK) return rc;
@@ -478,6 +483,7 @@ int envelope_rect(Run &R) {
     const bool stereo = P->channels == 2;
     const RectKernels K = P->dtype == BPMX_DT_U8    ? rect_kernels<BPMX_DT_U8>(stereo)
                           : P->dtype == BPMX_DT_I16 ? rect_kernels<BPMX_DT_I16>(stereo)
+                          : P->dtype == BPMX_DT_I24 ? rect_kernels<BPMX_DT_I24>(stereo)
                                                     : rect_kernels<BPMX_DT_I32>(stereo);
     if (E.route == RECT_INT_LDS) {
         LAUNCH(ctx, s, "k_rect_lds", K.lds, E.grid, dim3(RECT_T), E.lds, s, a);

@@ -235,6 +235,7 @@ __device__ __forceinline__ double nat_frame(const void *__restrict__ pcm, int ch
         case BPMX_DT_I16: return (double)((const int16_t *)pcm)[frame];
         case BPMX_DT_I32: return (double)((const int32_t *)pcm)[frame];
         case BPMX_DT_F32: return (double)((const float *)pcm)[frame];
+        case BPMX_DT_I24: return (double)(int32_t)((const pcm24 *)pcm)[frame];
         default: return ((const double *)pcm)[frame];
         }
     }
@@ -676,6 +677,169 @@ __global__ __launch_bounds__(64 * NM_WAVES, NM_MINW) void k_native_blocks_mfma(N
 }
 template __global__ void k_native_blocks_mfma<3>(NatBlockArgs, const nm_i4 *, const nm_i16 *, const double *);
 template __global__ void k_native_blocks_mfma<5>(NatBlockArgs, const nm_i4 *, const nm_i16 *, const double *);
+
+/* ---------------------------------------------------------------------- */
+/* Packed 24-bit mono (BPMX_DT_I24) on the matrix cores: k_native_blocks_mfma
+ * with one more plane.  The sample is the int32 v << 8 (bpmx_pcm.h) and
+ *     v = 65536 h + 256 (m - 128) + (l - 128) + 128 * 257
+ * with h the signed top byte and m - 128 = m ^ 0x80, l - 128 = l ^ 0x80 the two
+ * lower bytes as int8.  With q = sum_j 256^j d_j (7 balanced digits, as above)
+ *     sum_i q_i v_i = 256 sum_r 256^r [ sum_i d_(r+1),i (l_i - 128) + d_r,i (m_i - 128) + d_(r-1),i h_i ]
+ *                     + sum_i d_0,i (l_i - 128) + 128 * 257 sum_i q_i.
+ * The brackets r = 0..7 are the 8 int32 accumulator rows of the same two M
+ * tiles (three A-fragment variants per K step, one per plane: six MFMAs per N
+ * tile and K step).  The loose term sum_i d_0,i (l_i - 128) — the lowest
+ * coefficient digit against the lowest sample byte, below 2^-54 of the
+ * column's full-scale sum, less than the f64 rounding of the result — is left
+ * out with its share 128 sum d_0 of the constant, which keeps 8 rows (a ninth
+ * would need a third M tile and 60 more VGPRs of fragments); the rest of the
+ * constant, 128 (D_r + D_(r+1)) per row with D_j = sum_i d_j,i, is the
+ * accumulators' start value.  |row| <= 3 * 160 * 2^14 + 2 * 160 * 2^14 < 2^24,
+ * so the rows combine in f64 exactly (four rows < 2^49 per half), H 2^32 + L
+ * is the one rounding, and the scale 2^(e_c - P + 16) (the rows' base 256 and
+ * the sample's << 8) is exact.
+ *
+ * Transport: the same slots, waves and DMA count as above, addressed in bytes.
+ * pcm may have any alignment: a tile's DMA starts at the 16-byte boundary at
+ * or below its first byte and never passes the one at or above the batch's
+ * last byte (include/bpmx.h), so there is no tail to patch.  A lane's 16
+ * samples of a K step are 48 bytes at any byte offset: 13 aligned LDS dwords,
+ * 12 funnel shifts, and per 12 bytes (4 samples) two v_perm_b32 per plane with
+ * constant selectors.  A slot holds nm24_tile_blocks(ds, KS) blocks (40 at
+ * ds = 146); the second N tile is skipped when they fit the first. */
+template <int KS>
+__global__ __launch_bounds__(64 * NM_WAVES, NM_MINW) void k_native_blocks_mfma24(NatBlockArgs A,
+                                                                                 const nm_i4 *__restrict__ afrag,
+                                                                                 const nm_i16 *__restrict__ ainit,
+                                                                                 const double *__restrict__ cscale) {
+    typedef nat_u4 u4;
+    __shared__ u4 slots[NM_WAVES][NM_SLOT_CH];
+    __shared__ double s_et[ET_SIZE];
+    __shared__ nm_i16 s_init[4];                        /* accumulator start values [M tile][lane half] */
+    nat_stage_epilogue_tables(A, s_et);
+    for (int i = threadIdx.x; i < 4; i += blockDim.x) s_init[i] = ainit[(i >> 1) * 64 + (i & 1) * 32];
+    const int lane = lane_id(), hf = lane >> 5, wv = __builtin_amdgcn_readfirstlane(wave_id());
+    const uintptr_t base = (uintptr_t)A.pcm;
+    const int ds = A.ds, bt = A.bt;
+    const int nch = (15 + 3 * (bt * ds + 1) + 15) >> 4;   /* <= NM_SLOT_CH (host: nm24_tile_blocks) */
+    nm_i4 af[2][KS][3];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+#pragma unroll
+            for (int v = 0; v < 3; ++v) af[t][s][v] = afrag[((t * KS + s) * 3 + v) * 64 + lane];
+    double sc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sc[q] = cscale[2 * q + hf];
+    __syncthreads();                                      /* s_et, s_init */
+
+    /* exactly NM_NDMA instructions per tile, every lane on (the vmcnt wait
+     * counts them): chunks past the tile or the batch re-read the batch's last
+     * chunk, the one that ends at the 16-byte boundary at or above its end */
+    const uintptr_t cend = (base + 3 * (uintptr_t)A.total + 15) & ~(uintptr_t)15, clast = cend - 16;
+    auto dma = [&](int64_t s0, u4 *slot) {
+        const uintptr_t a0 = (base + 3 * (uintptr_t)s0) & ~(uintptr_t)15;
+        int nchv = nch, lanev = lane;                     /* opaque: no hoisted lane masks (k_native_blocks_mfma) */
+        asm volatile("" : "+s"(nchv), "+v"(lanev));
+#pragma unroll
+        for (int r = 0; r < NM_NDMA; ++r) {
+            const int q = r * 64 + lanev;
+            uintptr_t c = a0 + (uintptr_t)q * 16;
+            c = (q < nchv && c + 16 <= cend) ? c : clast;
+            const uint32_t m0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)(slot + r * 64);
+            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" BPMX_NM_POLICY
+                         :: "v"((const char *)c), "s"(m0) : "memory");
+        }
+    };
+    const int64_t stride = (int64_t)gridDim.x * NM_WAVES;
+    int64_t t = (int64_t)blockIdx.x * NM_WAVES + wv;
+    u4 *const slot = slots[wv];
+    NatTile tl{};
+    if (t < A.n_tiles) tl = nat_tile_ld(A.tiles, t);
+    if (t < A.n_tiles) dma(tl.s0, slot);
+    for (; t < A.n_tiles; t += stride) {
+        const int64_t tr = t + stride;                          /* the tile this slot is refilled with */
+        NatTile tn{};
+        if (tr < A.n_tiles) tn = nat_tile_ld(A.tiles, tr);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_setprio(2);
+        const int coff = (int)((base + 3 * (uintptr_t)tl.s0) & 15);
+        const int Lt = tl.nb - tl.j0 < bt ? tl.nb - tl.j0 : bt;
+        const uint32_t *tw = (const uint32_t *)slot;
+        double res[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            if (n == 1 && bt <= 32) break;                        /* wave-uniform: one N tile holds the slot's blocks */
+            const int b = 32 * n + (lane & 31);
+            const int by0 = coff + 3 * ((b < Lt ? b : 0) * ds + 16 * hf);   /* byte index of the k-group's start */
+            const uint32_t sh = (uint32_t)(by0 & 3) * 8u;
+            nm_i16 acc0 = s_init[hf], acc1 = s_init[2 + hf];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const uint32_t *p = tw + ((by0 + 96 * s) >> 2);
+                uint32_t w[13];
+#pragma unroll
+                for (int i = 0; i < 13; ++i) w[i] = p[i];
+                nm_i4 bh, bm, bl;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    /* 12 bytes l0 m0 h0 l1 m1 h1 l2 m2 h2 l3 m3 h3 */
+                    const uint32_t e0 = __builtin_amdgcn_alignbit(w[3 * i + 1], w[3 * i], sh);
+                    const uint32_t e1 = __builtin_amdgcn_alignbit(w[3 * i + 2], w[3 * i + 1], sh);
+                    const uint32_t e2 = __builtin_amdgcn_alignbit(w[3 * i + 3], w[3 * i + 2], sh);
+                    bl[i] = (int32_t)(__builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00060300u), 0x05020100u) ^
+                                      0x80808080u);
+                    bm[i] = (int32_t)(__builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00070401u), 0x06020100u) ^
+                                      0x80808080u);
+                    bh[i] = (int32_t)__builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00000502u), 0x07040100u);
+                }
+                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][s][0], bl, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][s][0], bl, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][s][1], bm, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][s][1], bm, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][s][2], bh, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][s][2], bh, acc1, 0, 0, 0);
+            }
+            /* |row| < 2^24: four rows a_r 256^r combine below 2^49, exact in
+             * f64 FMAs; H 2^32 + L is the one rounding */
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double L = __builtin_fma((double)acc0[4 * q + 3], 16777216.0,
+                                 __builtin_fma((double)acc0[4 * q + 2], 65536.0,
+                                 __builtin_fma((double)acc0[4 * q + 1], 256.0, (double)acc0[4 * q])));
+                const double H = __builtin_fma((double)acc1[4 * q + 3], 16777216.0,
+                                 __builtin_fma((double)acc1[4 * q + 2], 65536.0,
+                                 __builtin_fma((double)acc1[4 * q + 1], 256.0, (double)acc1[4 * q])));
+                res[n][q] = __builtin_fma(H, 4294967296.0, L) * sc[q];
+            }
+        }
+        const int j = tl.j0 + lane;
+        const bool valid = lane < bt && j < tl.nb;
+        double x0 = 0.0;
+        if (valid) {
+            const uint8_t *sb = (const uint8_t *)slot + coff + 3 * lane * ds;
+            x0 = (double)(int32_t)((uint32_t)sb[0] << 8 | (uint32_t)sb[1] << 16 | (uint32_t)sb[2] << 24);
+        }
+        /* the slot is read: refill it with the next tile, which flies during this epilogue */
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (tr < A.n_tiles) dma(tn.s0, slot);
+        __builtin_amdgcn_s_setprio(0);
+        /* lane half 0 holds even coefficients, half 1 odd ones; N tile n = blocks 32n.. */
+        double cf[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const double other = __shfl_xor(hf ? res[0][q] : res[1][q], 32);
+            cf[2 * q] = hf ? other : res[0][q];
+            cf[2 * q + 1] = hf ? res[1][q] : other;
+        }
+        nat_tile_epilogue(A, s_et, tl, t, lane, valid, V4{cf[0], cf[1], cf[2], cf[3]}, V4{cf[4], cf[5], cf[6], cf[7]},
+                          x0);
+        tl = tn;
+    }
+}
+template __global__ void k_native_blocks_mfma24<3>(NatBlockArgs, const nm_i4 *, const nm_i16 *, const double *);
+template __global__ void k_native_blocks_mfma24<5>(NatBlockArgs, const nm_i4 *, const nm_i16 *, const double *);
 
 /* ---------------------------------------------------------------------- */
 
@@ -1800,6 +1964,63 @@ std::vector<int32_t> build_mfma(const std::vector<LD> &cl, int R, int KS) {
     return w;
 }
 
+/* tables for k_native_blocks_mfma24, build_mfma's layout with three fragment
+ * variants: accumulator row rho of coefficient c takes digit rho + 1 - v of q
+ * against plane v (0: low byte, 1: middle byte, 2: top byte); the start value
+ * of row rho is 128 (D_rho + D_(rho+1)); the scale carries the rows' base 256
+ * and the sample's << 8. */
+std::vector<int32_t> build_mfma24(const std::vector<LD> &cl, int R, int KS) {
+    std::vector<int64_t> q((size_t)R * 8);
+    std::vector<double> scale(8);
+    for (int c = 0; c < 8; ++c) {
+        LD mx = 0;
+        for (int i = 0; i < R; ++i) mx = std::max(mx, fabsl(cl[(size_t)i * 8 + c]));
+        int e = 0;
+        if (mx > 0) frexpl(mx, &e);                          /* mx < 2^e */
+        scale[c] = ldexp(1.0, e - NM_P + 16);
+        for (int i = 0; i < R; ++i) q[(size_t)i * 8 + c] = llroundl(ldexpl(cl[(size_t)i * 8 + c], NM_P - e));
+    }
+    std::vector<int8_t> d((size_t)R * 64, 0);                /* d[(k * 8 + c) * 8 + j], j < NM_D */
+    for (int i = 0; i < R * 8; ++i) {
+        int64_t v = q[i];
+        for (int r = 0; r < NM_D; ++r) {
+            int dg = (int)(v & 255);
+            if (dg >= 128) dg -= 256;
+            d[(size_t)i * 8 + r] = (int8_t)dg;
+            v = (v - dg) >> 8;
+        }
+    }
+    auto dig = [&](int k, int c, int j) -> int { return (k < R && j >= 0 && j < NM_D) ? d[((size_t)k * 8 + c) * 8 + j] : 0; };
+    auto dsum = [&](int c, int j) -> int64_t {
+        int64_t sum = 0;
+        for (int k = 0; k < R; ++k) sum += dig(k, c, j);
+        return sum;
+    };
+    std::vector<int32_t> w(16 + 2 * 64 * 16 + (size_t)2 * KS * 3 * 64 * 4, 0);
+    std::memcpy(w.data(), scale.data(), 64);
+    int32_t *init = w.data() + 16;
+    for (int t = 0; t < 2; ++t)
+        for (int l = 0; l < 64; ++l)
+            for (int reg = 0; reg < 16; ++reg) {
+                const int c = 2 * (reg >> 2) + (l >> 5), rho = 4 * t + (reg & 3);
+                init[(t * 64 + l) * 16 + reg] = (int32_t)(128 * (dsum(c, rho) + dsum(c, rho + 1)));
+            }
+    int32_t *af = init + 2 * 64 * 16;
+    for (int t = 0; t < 2; ++t)
+        for (int st = 0; st < KS; ++st)
+            for (int v = 0; v < 3; ++v)
+                for (int l = 0; l < 64; ++l) {
+                    const int row = l & 31;
+                    const int c = 2 * (row >> 3) + ((row >> 2) & 1), j = 4 * t + (row & 3) + 1 - v;
+                    for (int b = 0; b < 16; ++b) {
+                        const int k = 32 * st + 16 * (l >> 5) + b;
+                        const uint32_t byte = (uint8_t)(int8_t)dig(k, c, j);
+                        af[(((t * KS + st) * 3 + v) * 64 + l) * 4 + b / 4] |= (int32_t)(byte << (8 * (b & 3)));
+                    }
+                }
+    return w;
+}
+
 /* tables for k_native_blocks_mfma_big (v_mfma_i32_16x16x64_i8), the digits of build_mfma
  * with K = CH x R, each coefficient repeated for the CH interleaved channels:
  *   [0, 16) scale | [16, 80) initial accumulators [M tile m][lane group g][4]
@@ -1917,6 +2138,7 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
     const bool use_mfma = np.route == NAT_R_MFMA3 || np.route == NAT_R_MFMA5;
     const bool use_big = np.route == NAT_R_BIG5 || np.route == NAT_R_BIG10;
     const bool use_dma = np.route == NAT_R_DMA1 || np.route == NAT_R_DMA2;
+    const bool use_m24 = np.route == NAT_R_M24_3 || np.route == NAT_R_M24_5;
     std::vector<int64_t> key(17);
     for (int i = 0; i < 12; ++i) std::memcpy(&key[i], &P->sos[i], 8);
     key[12] = ds;
@@ -1934,7 +2156,7 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
             ctx->nat_tab.resize(o + w.size() / 2);
             std::memcpy(ctx->nat_tab.data() + o, w.data(), w.size() * 4);
         } else if (mfma_ks) {
-            const std::vector<int32_t> w = build_mfma(cl, ds + 1, mfma_ks);
+            const std::vector<int32_t> w = use_m24 ? build_mfma24(cl, ds + 1, mfma_ks) : build_mfma(cl, ds + 1, mfma_ks);
             const size_t o = ctx->nat_tab.size();
             ctx->nat_tab.resize(o + w.size() / 2);
             std::memcpy(ctx->nat_tab.data() + o, w.data(), w.size() * 4);
@@ -2019,6 +2241,17 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
             else
                 LAUNCH(ctx, s, "k_native_blocks", k_native_blocks_mfma<5>, dim3(g1), dim3(64 * NM_WAVES), 0, s, a, af,
                        init, mt);
+        } else if (use_m24) {
+            const double *mt = d_tab + mfma_off;
+            const nm_i16 *init = (const nm_i16 *)(mt + 8);
+            const nm_i4 *af = (const nm_i4 *)(mt + 8 + 2 * 64 * 16 / 2);
+            const unsigned g1 = (unsigned)std::min<int64_t>((nt + NM_WAVES - 1) / NM_WAVES, 256 * 2);
+            if (mfma_ks == 3)
+                LAUNCH(ctx, s, "k_native_blocks", k_native_blocks_mfma24<3>, dim3(g1), dim3(64 * NM_WAVES), 0, s, a, af,
+                       init, mt);
+            else
+                LAUNCH(ctx, s, "k_native_blocks", k_native_blocks_mfma24<5>, dim3(g1), dim3(64 * NM_WAVES), 0, s, a, af,
+                       init, mt);
         } else if (use_big) {
             a.total = foff[F] * P->channels;                 /* int16 elements */
             const double *mt = d_tab + mfma_off;
@@ -2063,6 +2296,7 @@ int native_envelope(bpmx_ctx *ctx, const bpmx_params *P, const bpmx_batch *B, co
             case BPMX_DT_I16: NAT_GEN(BPMX_DT_I16) break;
             case BPMX_DT_I32: NAT_GEN(BPMX_DT_I32) break;
             case BPMX_DT_F32: NAT_GEN(BPMX_DT_F32) break;
+            case BPMX_DT_I24: NAT_GEN(BPMX_DT_I24) break;
             default: NAT_GEN(BPMX_DT_F64) break;
             }
 #undef NAT_GEN

@@ -43,11 +43,18 @@ template <> struct Pcm<BPMX_DT_I16> { typedef int16_t T; };
 template <> struct Pcm<BPMX_DT_I32> { typedef int32_t T; };
 template <> struct Pcm<BPMX_DT_F32> { typedef float T; };
 template <> struct Pcm<BPMX_DT_F64> { typedef double T; };
+template <> struct Pcm<BPMX_DT_I24> { typedef pcm24 T; };   /* the int32 sample v << 8 (bpmx_pcm.h) */
 
 template <int DT, bool MULTI>
 __device__ __forceinline__ double frame_at(const void *__restrict__ pcm, int ch, int64_t frame) {
     typedef typename Pcm<DT>::T T;
     const T *p = (const T *)pcm;
+    if (DT == BPMX_DT_I24) {                         /* through int32, the sample's value */
+        if (!MULTI) return (double)(int32_t)p[frame];
+        double s = (double)(int32_t)p[frame * ch];
+        for (int c = 1; c < ch; ++c) s = s + (double)(int32_t)p[frame * ch + c];
+        return s / (double)ch;
+    }
     if (!MULTI) return (double)p[frame];
     if (DT == BPMX_DT_F32) {
         const float *q = (const float *)pcm + frame * ch;
@@ -638,6 +645,8 @@ template __global__ void k_ref_pick<BPMX_DT_I16, false>(EnvRefArgs);
 template __global__ void k_ref_pick<BPMX_DT_I32, false>(EnvRefArgs);
 template __global__ void k_ref_pick<BPMX_DT_F32, false>(EnvRefArgs);
 template __global__ void k_ref_pick<BPMX_DT_F64, false>(EnvRefArgs);
+template __global__ void k_ref_pick<BPMX_DT_I24, false>(EnvRefArgs);
+template __global__ void k_ref_pick<BPMX_DT_I24, true>(EnvRefArgs);
 template __global__ void k_ref_pick<BPMX_DT_U8, true>(EnvRefArgs);
 template __global__ void k_ref_pick<BPMX_DT_I16, true>(EnvRefArgs);
 template __global__ void k_ref_pick<BPMX_DT_I32, true>(EnvRefArgs);

@@ -39,6 +39,7 @@ template <int DT> struct RPcm;
 template <> struct RPcm<BPMX_DT_U8> { typedef uint8_t T; typedef int32_t A; };
 template <> struct RPcm<BPMX_DT_I16> { typedef int16_t T; typedef int32_t A; };
 template <> struct RPcm<BPMX_DT_I32> { typedef int32_t T; typedef int64_t A; };
+template <> struct RPcm<BPMX_DT_I24> { typedef pcm24 T; typedef int64_t A; };   /* the int32 samples v << 8 (bpmx_pcm.h) */
 static_assert(RECT_LDS_N * 65536 < (int64_t(1) << 31), "32-bit local prefixes");
 
 /* the rectified integers of the m frames from absolute frame fr0 into sh[0, m).
@@ -52,27 +53,28 @@ __device__ __forceinline__ void rect_load(const void *__restrict__ pcm, int64_t 
     typedef typename RPcm<DT>::T T;
     typedef typename RPcm<DT>::A A;
     constexpr int C = ST ? 2 : 1;
-    constexpr int FB = (int)sizeof(T) * C;           /* bytes per frame: 1, 2, 4 or 8 */
+    constexpr int FB = (int)sizeof(T) * C;           /* bytes per frame: 1, 2, 4 or 8; packed 24-bit: 3 or 6 */
     constexpr int FPV = 16 / FB;
+    constexpr int WDT = DT == BPMX_DT_I24 ? BPMX_DT_I32 : DT;    /* np.abs wraps in the working dtype */
     const char *p = (const char *)pcm + fr0 * FB;
     const uintptr_t a = (uintptr_t)p;
     int head = m, nvec = 0;
-    if (a % FB == 0) {
+    if (16 % FB == 0 && a % FB == 0) {               /* packed 24-bit frames straddle the vectors: one by one */
         head = (int)(((16 - (a & 15)) & 15) / FB);
         if (head > m) head = m;
         nvec = (m - head) / FPV;
     }
     const int tail = head + nvec * FPV;
     const int tid = threadIdx.x;
-    auto one = [&](int j) { sh[j] = (A)rect_int_frame<T>(DT, ST, (const T *)(p + (int64_t)j * FB)); };
+    auto one = [&](int j) { sh[j] = (A)rect_int_frame<T>(WDT, ST, (const T *)(p + (int64_t)j * FB)); };
     for (int j = tid; j < head; j += RECT_T) one(j);
     const uint4 *__restrict__ pv = (const uint4 *)(p + (int64_t)head * FB);
     for (int v = tid; v < nvec; v += RECT_T) {
         const uint4 q = pv[v];
-        T e[16 / sizeof(T)];
+        T e[(16 + sizeof(T) - 1) / sizeof(T)];       /* nvec is 0 for packed 24-bit */
         __builtin_memcpy(e, &q, 16);
 #pragma unroll
-        for (int k = 0; k < FPV; ++k) sh[head + v * FPV + k] = (A)rect_int_frame<T>(DT, ST, e + k * C);
+        for (int k = 0; k < FPV; ++k) sh[head + v * FPV + k] = (A)rect_int_frame<T>(WDT, ST, e + k * C);
     }
     for (int j = tail + tid; j < m; j += RECT_T) one(j);
 }
@@ -282,17 +284,23 @@ template __global__ void k_rect_lds<BPMX_DT_I16, false>(RectArgs);
 template __global__ void k_rect_lds<BPMX_DT_I16, true>(RectArgs);
 template __global__ void k_rect_lds<BPMX_DT_I32, false>(RectArgs);
 template __global__ void k_rect_lds<BPMX_DT_I32, true>(RectArgs);
+template __global__ void k_rect_lds<BPMX_DT_I24, false>(RectArgs);
+template __global__ void k_rect_lds<BPMX_DT_I24, true>(RectArgs);
 template __global__ void k_rect_csum<BPMX_DT_U8, false>(RectArgs);
 template __global__ void k_rect_csum<BPMX_DT_U8, true>(RectArgs);
 template __global__ void k_rect_csum<BPMX_DT_I16, false>(RectArgs);
 template __global__ void k_rect_csum<BPMX_DT_I16, true>(RectArgs);
 template __global__ void k_rect_csum<BPMX_DT_I32, false>(RectArgs);
 template __global__ void k_rect_csum<BPMX_DT_I32, true>(RectArgs);
+template __global__ void k_rect_csum<BPMX_DT_I24, false>(RectArgs);
+template __global__ void k_rect_csum<BPMX_DT_I24, true>(RectArgs);
 template __global__ void k_rect_gout<BPMX_DT_U8, false>(RectArgs);
 template __global__ void k_rect_gout<BPMX_DT_U8, true>(RectArgs);
 template __global__ void k_rect_gout<BPMX_DT_I16, false>(RectArgs);
 template __global__ void k_rect_gout<BPMX_DT_I16, true>(RectArgs);
 template __global__ void k_rect_gout<BPMX_DT_I32, false>(RectArgs);
 template __global__ void k_rect_gout<BPMX_DT_I32, true>(RectArgs);
+template __global__ void k_rect_gout<BPMX_DT_I24, false>(RectArgs);
+template __global__ void k_rect_gout<BPMX_DT_I24, true>(RectArgs);
 
 }  // namespace bpmx

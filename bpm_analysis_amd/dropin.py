@@ -75,7 +75,11 @@ def _warn_ties(flags: int, what: str) -> None:
         logging.debug(ORDERED_MSG.format(what=what))
 
 
-def _read_wav(file_path: str):
+def _read_wav(file_path: str, packed24: bool = False):
+    """scipy's read; packed24: a plain 24-bit PCM file as ``pcm24.Pcm24``, its samples not expanded."""
+    if packed24:
+        from .pcm24 import read_wav
+        return read_wav(file_path)
     from scipy.io import wavfile
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -256,7 +260,7 @@ def analyze_batch(recordings: Sequence[np.ndarray], fs: int, params: Dict, mode:
 
 
 def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory: str, mode: str = None,
-                      device: int = 0) -> List[dict]:
+                      device: int = 0, packed24: bool = False) -> List[dict]:
     """Batched file entry point: what ``preprocess_audio`` + the noise floor +
     the raw-peak call do per file (bpm_analysis.py:1007-1062, :1064-1117,
     :223-229), for many WAV files in few launch sequences.
@@ -268,7 +272,11 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
     WAVs of the reference are written (next to the input and into
     ``output_directory``).  Returns one dict per path, in order: env, floor,
     troughs, peaks, sr, flags, or ``error`` (the exception the reference would
-    raise for that file, e.g. the filtfilt padlen ValueError)."""
+    raise for that file, e.g. the filtfilt padlen ValueError).
+
+    ``packed24=True``: 24-bit PCM files are read by ``pcm24.read_wav`` and
+    uploaded as they lie in the file (3 bytes per sample, a format group of
+    their own); the results are those of the int32 array scipy makes of them."""
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
     rect = mode == RECTIFIED
@@ -281,7 +289,7 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
     audio = []
     for k, path in enumerate(file_paths):
         try:
-            fs, a = _read_wav(path)
+            fs, a = _read_wav(path, packed24)
         except Exception as exc:                      # wavfile errors propagate per file, as in the GUI loop
             out[k] = {"error": exc}
             audio.append(None)
@@ -323,7 +331,8 @@ def analyze_wav_files(file_paths: Sequence[str], params: Dict, output_directory:
 def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output_directory: str,
                                  start_bpm_hints: Sequence = None, original_file_paths: Sequence[str] = None,
                                  mode: str = None, device: int = 0, plot: bool = False, labels: bool = False,
-                                 label_gap_sec: float = 5.0, labels_overwrite: bool = False) -> List[dict]:
+                                 label_gap_sec: float = 5.0, labels_overwrite: bool = False,
+                                 packed24: bool = False) -> List[dict]:
     """``beats.analyze_wav_file`` for many WAV files with every stage on the
     device: per file ``<base>_bpm_plot.csv``, ``<base>_Analysis_Summary.md``,
     ``<base>_Debug_Log.md`` and ``<base>_Analysis_Settings.json`` (and both
@@ -336,7 +345,8 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     every ``plot_downsample_factor``-th sample), everything else from the
     tables, through ``plot.write_plot_packed``.
 
-    Files are read and grouped as ``analyze_wav_files`` does; each group is one
+    Files are read and grouped as ``analyze_wav_files`` does (``packed24``
+    included); each group is one
     ``Detector.run_host_reports``: hot path, tables, beat stages with one start
     hint per file and the decision trace, final metrics, all on the GPU, and
     ``explain`` + ``reports.write_reports_packed`` on the host.  No
@@ -380,7 +390,7 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     audio = []
     for k, path in enumerate(file_paths):
         try:
-            fs, a = _read_wav(path)
+            fs, a = _read_wav(path, packed24)
         except Exception as exc:                      # wavfile errors propagate per file, as in the GUI loop
             out[k] = {"error": exc}
             audio.append(None)

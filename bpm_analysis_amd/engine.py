@@ -47,6 +47,25 @@ def _torch():
 _TORCH_DT = None
 
 
+def _flatten_batch(recordings):
+    """A host batch as one flat array -> (host, frame offsets, channels,
+    sample_format).  Recordings are numpy arrays (frames,) / (frames, channels)
+    or ``pcm24.Pcm24``; a batch is one sample format and channel count."""
+    from .pcm24 import Pcm24
+    packed = isinstance(recordings[0], Pcm24)
+    dt = recordings[0].dtype
+    ch = 1 if recordings[0].ndim == 1 else recordings[0].shape[1]
+    for r in recordings:
+        if isinstance(r, Pcm24) != packed or (not packed and r.dtype != dt) or \
+                (1 if r.ndim == 1 else r.shape[1]) != ch:
+            raise ValueError("a batch needs one sample format and channel count")
+    fo = np.zeros(len(recordings) + 1, dtype=np.int64)
+    fo[1:] = np.cumsum([r.shape[0] for r in recordings])
+    if packed:
+        return np.concatenate([r.data for r in recordings]), fo, ch, "i24"
+    return np.concatenate([np.ascontiguousarray(r).reshape(-1) for r in recordings]), fo, ch, None
+
+
 def torch_dtype(np_dtype):
     global _TORCH_DT
     torch = _torch()
@@ -740,9 +759,11 @@ class Detector:
     def run(self, pcm, frame_offsets: Sequence[int], fs: int, params: dict, mode: str = "reference",
             stages: int = N.STAGE_ALL, channels: int = 1, out: Optional[Result] = None, want_y: bool = False,
             d: Optional[Design] = None, log: bool = False, options: int = 0,
-            order: Optional[N.PeakOrder] = None) -> Result:
+            order: Optional[N.PeakOrder] = None, sample_format: Optional[str] = None) -> Result:
         """Run `stages` over a device batch.  `pcm` is a CUDA tensor (or None when
         ENVELOPE is not requested and `out.env` already holds the envelopes).
+        `sample_format="i24"`: `pcm` is a uint8 tensor of packed 24-bit samples
+        (3 bytes each, little-endian; BPMX_DT_I24), at any byte offset.
         `order`: bpmx_run_ordered's candidate export / visiting ranks (see
         ``resolve_ties``)."""
         _no_filtered_signal(mode, want_y or (out is not None and out.y is not None))
@@ -751,11 +772,17 @@ class Detector:
         fo = np.ascontiguousarray(frame_offsets, dtype=np.int64)
         if out is None:
             out = self.alloc(fo, d.ds, d.sr, want_y=want_y)
+        if sample_format not in (None, "i24"):
+            raise ValueError(f"unknown sample_format {sample_format!r} (None or 'i24')")
         if pcm is not None:
             np_dt = {v: k for k, v in _torch_np_map().items()}[pcm.dtype]
-            dt = dtype_code(np_dt)
+            dt, width = dtype_code(np_dt), 1
+            if sample_format == "i24":
+                if np_dt != np.dtype(np.uint8):
+                    raise TypeError("sample_format='i24' needs a uint8 tensor of packed samples")
+                dt, width = N.DT_I24, 3
             assert pcm.is_cuda and pcm.is_contiguous()
-            assert pcm.numel() >= int(fo[-1]) * channels, "pcm shorter than frame_offsets[-1] * channels"
+            assert pcm.numel() >= int(fo[-1]) * channels * width, "pcm shorter than frame_offsets[-1] * channels"
             pcm_ptr = pcm.data_ptr()
         else:
             dt, pcm_ptr = N.DT_I16, None
@@ -982,18 +1009,11 @@ class Detector:
             for k, i in enumerate(perm):
                 out[i] = res[k]
             return out
-        dt = recordings[0].dtype
-        ch = 1 if recordings[0].ndim == 1 else recordings[0].shape[1]
-        for r in recordings:
-            if r.dtype != dt or (1 if r.ndim == 1 else r.shape[1]) != ch:
-                raise ValueError("a batch needs one sample format and channel count")
-        fo = np.zeros(len(recordings) + 1, dtype=np.int64)
-        fo[1:] = np.cumsum([r.shape[0] for r in recordings])
-        host = np.concatenate([np.ascontiguousarray(r).reshape(-1) for r in recordings])
+        host, fo, ch, fmt = _flatten_batch(recordings)
         with self.lock, torch.cuda.stream(self.host_stream()):
             pcm = torch.from_numpy(host).to(self.device)
             res = self.run(pcm, fo, fs, params, mode=mode, stages=stages, channels=ch, want_y=want_y, log=log,
-                           options=options)
+                           options=options, sample_format=fmt)
             if resolve_ties:
                 self.resolve_ties(res, params, stages, options)
             out = res.to_host()          # .cpu() waits for this stream only
@@ -1127,19 +1147,12 @@ class Detector:
         """Upload one batch, run it and re-decide its ties (the caller holds the
         lock and has the host stream current) -> (Result, Design)."""
         torch = _torch()
-        dt = recordings[0].dtype
-        ch = 1 if recordings[0].ndim == 1 else recordings[0].shape[1]
-        for r in recordings:
-            if r.dtype != dt or (1 if r.ndim == 1 else r.shape[1]) != ch:
-                raise ValueError("a batch needs one sample format and channel count")
-        fo = np.zeros(len(recordings) + 1, dtype=np.int64)
-        fo[1:] = np.cumsum([r.shape[0] for r in recordings])
-        host = np.concatenate([np.ascontiguousarray(r).reshape(-1) for r in recordings])
+        host, fo, ch, fmt = _flatten_batch(recordings)
         _no_filtered_signal(mode, want_y)
         d = mode_design(fs, params, mode)
         pcm = torch.from_numpy(host).to(self.device)
         res = self.run(pcm, fo, fs, params, mode=mode, stages=stages, channels=ch, want_y=want_y, d=d,
-                       options=options)
+                       options=options, sample_format=fmt)
         if resolve_ties:
             self.resolve_ties(res, params, stages, options)
         return res, d

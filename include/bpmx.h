@@ -55,11 +55,19 @@ extern "C" {
 /* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
  * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL;
  * bpmx_score_device and BPMX_OPT_SCORE_GLOBAL; bpmx_marks_device and
- * BPMX_OPT_MARKS_GLOBAL. */
+ * BPMX_OPT_MARKS_GLOBAL; BPMX_DT_I24. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
-enum bpmx_dtype { BPMX_DT_U8 = 0, BPMX_DT_I16 = 1, BPMX_DT_I32 = 2, BPMX_DT_F32 = 3, BPMX_DT_F64 = 4 };
+enum bpmx_dtype { BPMX_DT_U8 = 0, BPMX_DT_I16 = 1, BPMX_DT_I32 = 2, BPMX_DT_F32 = 3, BPMX_DT_F64 = 4,
+                  BPMX_DT_I24 = 5 };
+/* BPMX_DT_I24: packed 24-bit PCM as it lies in a WAV file: 3 bytes per element,
+ * little-endian, two's complement, frames interleaved; pcm may have any byte
+ * alignment and frame_offsets stay in frames.  In every mode and stage the
+ * batch means exactly the BPMX_DT_I32 batch whose samples are v << 8, v the
+ * sign-extended 24-bit value (what scipy.io.wavfile.read returns for the
+ * file).  Nothing is read past the 16-byte boundary at or above the batch's
+ * last byte. */
 
 /* REFERENCE: the shipped pipeline, bit-exact (stride pick, b/a filtfilt at the
  *            decimated rate, rolling-mean envelope; bpm_analysis.py:1031-1054).

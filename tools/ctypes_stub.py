@@ -21,6 +21,7 @@ LIB = os.environ.get("BPMX_LIB", os.path.join(HERE, "..", "bpm_analysis_amd", "l
 
 DT = {np.dtype(np.uint8): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 2, np.dtype(np.float32): 3,
       np.dtype(np.float64): 4}
+DT_I24 = 5      # packed 24-bit PCM (3 bytes per sample, any byte alignment): no numpy dtype; the int32 samples v << 8
 
 
 class Params(ctypes.Structure):          # bpmx_params
