@@ -77,7 +77,8 @@ EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy",
            "bpmx_run", "bpmx_run_ordered", "bpmx_pack", "bpmx_synth", "bpmx_synth_host", "bpmx_profile", "bpmx_profile_read", "bpmx_profile_only",
            "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
            "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot",
-           "bpmx_labels_device", "bpmx_score_device", "bpmx_marks_device"]
+           "bpmx_labels_device", "bpmx_score_device", "bpmx_marks_device", "bpmx_tempo_windows",
+           "bpmx_tempo_device"]
 
 
 class Params(ctypes.Structure):
@@ -192,6 +193,20 @@ class MarksParams(ctypes.Structure):
     _fields_ = [("smoothing_window_sec", ctypes.c_double)]
 
 
+class TempoParams(ctypes.Structure):
+    """bpmx_tempo_params: window, step and lag range in samples, the strength a
+    window counts from, and how many windows the hint may come from."""
+    _fields_ = [("win", ctypes.c_int32), ("hop", ctypes.c_int32), ("kmin", ctypes.c_int32), ("kmax", ctypes.c_int32),
+                ("min_strength", ctypes.c_double), ("start_windows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TempoOut(ctypes.Structure):
+    """bpmx_tempo_out: the device arrays bpmx_tempo_device fills (per window,
+    then per file; every pointer required)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("lag", "rho", "bpm", "n_valid", "n_strong", "median_bpm", "mean_rho",
+                                               "hint")]
+
+
 class BpmxError(RuntimeError):
     """A libbpmx failure.  ``code`` is the BPMX_E_* status (None when raised by
     the host side).  Only argument and size-limit errors belong to the
@@ -295,6 +310,12 @@ def load() -> ctypes.CDLL:
         L.bpmx_marks_device.argtypes = [P, I32, I32, ctypes.POINTER(MarksParams), ctypes.POINTER(RefMarks), P,
                                         ctypes.POINTER(PackedOut), ctypes.POINTER(BeatsOut), P, P, P]
         L.bpmx_marks_device.restype = ctypes.c_int
+    if hasattr(L, "bpmx_tempo_device"):
+        L.bpmx_tempo_windows.argtypes = [I64, I32, I32]
+        L.bpmx_tempo_windows.restype = I64
+        L.bpmx_tempo_device.argtypes = [P, I32, ctypes.POINTER(ctypes.c_int64), I32, I32,
+                                        ctypes.POINTER(TempoParams), ctypes.POINTER(Out), ctypes.POINTER(TempoOut), P]
+        L.bpmx_tempo_device.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

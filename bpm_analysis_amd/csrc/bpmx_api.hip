@@ -3,7 +3,7 @@
  * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
  * bpmx_pack_trough_floor, bpmx_pack_plot, bpmx_beats_device,
  * bpmx_beats_device_ex, bpmx_metrics_device, bpmx_labels_device,
- * bpmx_score_device and bpmx_marks_device.
+ * bpmx_score_device, bpmx_marks_device and bpmx_tempo_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -809,6 +809,68 @@ int bpmx_marks_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_mar
     HIP_TRY(hipSetDevice(ctx->device));
     return marks_stage(ctx, marks_plan(n_files, marks->cap_ref, ctx->options), n_files, sr, *params, *marks, nd,
                        *tables, *beats, gap, record, (hipStream_t)stream);
+}
+
+int64_t bpmx_tempo_windows(int64_t nd, int32_t win, int32_t hop) { return tempo_windows(nd, win, hop); }
+
+int bpmx_tempo_device(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t sr,
+                      const bpmx_tempo_params *params, const bpmx_out *in, const bpmx_tempo_out *out, void *stream) {
+    if (!ctx || !frame_offsets || !params || !in || !out) return fail(BPMX_E_ARG, "bpmx_tempo_device: NULL argument");
+    if (n_files < 0 || ds < 1 || sr < 1) return fail(BPMX_E_ARG, "bpmx_tempo_device: bad n_files/ds/sr");
+    const TempoPlan G = tempo_plan(params->win, params->hop, params->kmin, params->kmax);
+    if (G.status == BPMX_E_ARG)
+        return fail(BPMX_E_ARG, "bpmx_tempo_device: needs hop >= 1, 2 <= kmin <= kmax and kmax + 1 < win");
+    if (G.status != BPMX_OK)
+        return fail(BPMX_E_LIMIT, "bpmx_tempo_device: the window and its lag range exceed a workgroup's LDS "
+                                  "(8 * (win4 + kmax + 8 + 4 * (kmax - kmin + 4)) > " +
+                                      std::to_string((int)TEMPO_LDS_MAX) + " bytes)");
+    if (!(params->min_strength == params->min_strength) || params->start_windows < 0)
+        return fail(BPMX_E_ARG, "bpmx_tempo_device: needs a min_strength that is not NaN and start_windows >= 0");
+    if (n_files == 0) return BPMX_OK;
+    if (!in->env) return fail(BPMX_E_ARG, "bpmx_tempo_device: needs env");
+    if (!out->lag || !out->rho || !out->bpm || !out->n_valid || !out->n_strong || !out->median_bpm ||
+        !out->mean_rho || !out->hint)
+        return fail(BPMX_E_ARG, "bpmx_tempo_device: every pointer of bpmx_tempo_out is required");
+    /* doff | woff */
+    const size_t F = (size_t)n_files;
+    std::vector<int64_t> geo(2 * (F + 1));
+    int64_t *doff = geo.data(), *woff = doff + F + 1;
+    doff[0] = woff[0] = 0;
+    for (size_t f = 0; f < F; ++f) {
+        const int64_t n = frame_offsets[f + 1] - frame_offsets[f];
+        if (n < 0) return fail(BPMX_E_ARG, "frame offsets must be non-decreasing");
+        const int64_t nd = bpmx_decimated_length(n, ds);
+        if (nd >= (int64_t)INT_MAX / 2) return fail(BPMX_E_LIMIT, "recording too long");
+        doff[f + 1] = doff[f] + nd;
+        woff[f + 1] = woff[f] + tempo_windows(nd, params->win, params->hop);
+    }
+    const int64_t total = woff[F];
+    if (total >= (int64_t)INT_MAX) return fail(BPMX_E_LIMIT, "bpmx_tempo_device: too many windows");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = BPMX_OK;
+    bool grew = false;
+    int64_t *d_geo = (int64_t *)ctx->buf("tempo_geo", geo.size() * 8, &rc, &grew);
+    if (rc != BPMX_OK) return rc;
+    if (grew || geo != ctx->tempo_key) {
+        /* stream-ordered: launches of an earlier call still read the old geometry */
+        ctx->tempo_key.swap(geo);
+        HIP_TRY(hipMemcpyAsync(d_geo, ctx->tempo_key.data(), ctx->tempo_key.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    TempoArgs a{};
+    a.n_files = n_files; a.sr = sr; a.P = *params; a.G = G;
+    a.doff = d_geo; a.woff = d_geo + F + 1; a.env = in->env; a.O = *out;
+    if (total > 0) {
+        if (G.lags == 5) {
+            (void)hipFuncSetAttribute((const void *)k_tempo_valu<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TEMPO_LDS_MAX);
+            LAUNCH(ctx, s, "k_tempo_valu", k_tempo_valu<5>, dim3((unsigned)total), dim3(TEMPO_T), G.lds, s, a);
+        } else {
+            (void)hipFuncSetAttribute((const void *)k_tempo_valu<7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TEMPO_LDS_MAX);
+            LAUNCH(ctx, s, "k_tempo_valu", k_tempo_valu<7>, dim3((unsigned)total), dim3(TEMPO_T), G.lds, s, a);
+        }
+    }
+    LAUNCH(ctx, s, "k_tempo_record", k_tempo_record, dim3((unsigned)n_files), dim3(TEMPO_REC_T), 0, s, a);
+    return BPMX_OK;
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #define BPMX_KERNELS_H
 
 #include "bpmx_common.h"
+#include "bpmx_tempo_core.h"
 
 namespace bpmx {
 
@@ -692,6 +693,21 @@ struct MarksArgs {
 __global__ void k_marks_rows(MarksArgs A);
 __global__ void k_marks_scan(MarksArgs A);
 __global__ void k_marks_finish(MarksArgs A);
+
+/* bpmx_tempo_device (k_tempo.hip): one workgroup of TEMPO_T threads per
+ * (recording, window) pair, then one wave per recording for the record */
+struct TempoArgs {
+    int32_t n_files, sr;
+    bpmx_tempo_params P;
+    TempoPlan G;                /* bpmx_tempo_core.h tempo_plan */
+    const int64_t *doff;        /* [F+1] envelope offsets */
+    const int64_t *woff;        /* [F+1] window offsets: the prefix sums of bpmx_tempo_windows */
+    const double *env;
+    bpmx_tempo_out O;
+};
+template <int L>
+__global__ void k_tempo_valu(TempoArgs A);
+__global__ void k_tempo_record(TempoArgs A);
 
 /* Rectified-mode envelope (k_rect.hip): the centred rolling mean of |x| at the
  * native rate.  Integer PCM of one or two channels takes the exact-integer

@@ -332,7 +332,7 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                                  start_bpm_hints: Sequence = None, original_file_paths: Sequence[str] = None,
                                  mode: str = None, device: int = 0, plot: bool = False, labels: bool = False,
                                  label_gap_sec: float = 5.0, labels_overwrite: bool = False,
-                                 packed24: bool = False) -> List[dict]:
+                                 packed24: bool = False, tempo: bool = False) -> List[dict]:
     """``beats.analyze_wav_file`` for many WAV files with every stage on the
     device: per file ``<base>_bpm_plot.csv``, ``<base>_Analysis_Summary.md``,
     ``<base>_Debug_Log.md`` and ``<base>_Analysis_Settings.json`` (and both
@@ -366,6 +366,18 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     ``labels_written=False``, unless ``labels_overwrite=True``.  A file without
     reports gets no label file.
 
+    ``start_bpm_hints="auto"``: the tempo stage (``Detector.tempo_device``:
+    a BPM per 8 s window from the envelope's autocorrelation) runs on the
+    device and the beat stages start from its hint per file, read where it
+    lies; ``_Analysis_Settings.json`` records the value used, as it records a
+    typed hint.  ``tempo=True``: each dict gains ``tempo`` (the table and the
+    record, ``tempo.tempogram``'s dict) and ``tempo_check`` (``tempo.compare``
+    of the analysed BPM curve against it: the fractions of strong windows
+    where the curve agrees, is at twice or at half the window's BPM; None
+    without a strong window), and ``<base>_tempo.csv`` is written beside the
+    reports (``tempo.write_csv``).  With neither, the stage does not run and
+    every byte written is as before.
+
     Returns one dict per path, in order: ``run_host_reports``' dict, or
     ``error`` with the exception the reference raises for that file; as there,
     a file with fewer than two final beats gets no reports
@@ -373,10 +385,14 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     from .plot import write_plot_packed
     from .reports import write_reports_packed
     from . import labels as LB
+    from . import tempo as TP
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
     n = len(file_paths)
-    hints = [None] * n if start_bpm_hints is None else list(start_bpm_hints)
+    auto = isinstance(start_bpm_hints, str)
+    if auto and start_bpm_hints != "auto":
+        raise ValueError('start_bpm_hints is one entry per file or "auto"')
+    hints = [None] * n if start_bpm_hints is None or auto else list(start_bpm_hints)
     names = list(file_paths) if original_file_paths is None else list(original_file_paths)
     if len(hints) != n or len(names) != n:
         raise ValueError("start_bpm_hints and original_file_paths need one entry per file")
@@ -410,8 +426,9 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                 raise ValueError(DISTANCE_MSG)
             run_params = dict(params, save_filtered_wav=False) if rect else params
             res = det.run_host_reports([audio[k][1] for k in idx], fs, run_params, mode=mode,
-                                       hints=[hints[k] for k in idx], plot=plot,
-                                       **(dict(labels=True, label_gap_sec=label_gap_sec) if labels else {}))
+                                       hints="auto" if auto else [hints[k] for k in idx], plot=plot,
+                                       **(dict(labels=True, label_gap_sec=label_gap_sec) if labels else {}),
+                                       **(dict(tempo=True) if tempo else {}))
         except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
@@ -431,10 +448,16 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                 continue
             if labels:
                 r["labels_written"] = False
+            if auto:
+                hints[k] = r["start_bpm_hint"]
+            if tempo:
+                r["tempo_check"] = TP.compare(r["tempo"], r.get("bpm_times", ()), r.get("bpm", ()))
             if r["final_metrics"] is not None:
                 if plot:
                     r["figure"] = write_plot_packed(names[k], output_directory, params, r)
                 write_reports_packed(names[k], output_directory, r, hints[k])
+                if tempo:
+                    TP.write_csv(TP.tempo_path(names[k], output_directory), r["tempo"], r["tempo_check"])
                 if labels and r["labels"] is not None:
                     r["labels_written"] = LB.write_labels(LB.labels_path(names[k], output_directory), r["labels"],
                                                           overwrite=labels_overwrite)
@@ -459,7 +482,8 @@ def score_wav_files(file_paths: Sequence[str], params_list: Sequence[Dict], labe
     saves it).  A file that cannot be read, or whose label file is missing,
     unreadable or without an S1 / S2 mark, is a per-file ``error`` entry; the
     others still score.  Files are grouped by (rate, format, channels) as
-    ``analyze_wav_files`` groups them.
+    ``analyze_wav_files`` groups them.  ``start_bpm_hints="auto"``: the tempo
+    stage runs once per group on the shared envelope and feeds its hints.
 
     Returns one dict per setting, in order: ``params``, ``files`` (per path
     ``labels.score_summary``'s dict with ``record`` and ``status``, or
@@ -470,7 +494,10 @@ def score_wav_files(file_paths: Sequence[str], params_list: Sequence[Dict], labe
     if mode is None:
         mode = params_list[0].get("bpmx_mode", "reference") if params_list else "reference"
     n = len(file_paths)
-    hints = [None] * n if start_bpm_hints is None else list(start_bpm_hints)
+    auto = isinstance(start_bpm_hints, str)
+    if auto and start_bpm_hints != "auto":
+        raise ValueError('start_bpm_hints is one entry per file or "auto"')
+    hints = [None] * n if start_bpm_hints is None or auto else list(start_bpm_hints)
     if label_paths is None:
         label_paths = [LB.labels_path(p, os.path.dirname(p)) for p in file_paths]
     if len(hints) != n or len(label_paths) != n:
@@ -498,7 +525,8 @@ def score_wav_files(file_paths: Sequence[str], params_list: Sequence[Dict], labe
     for (fs, _, _), idx in groups.items():
         try:
             rec, st = det.score_sweep([audio[k] for k in idx], fs, params_list, [refs[k] for k in idx], mode=mode,
-                                      hints=[hints[k] for k in idx], tol_sec=tol_sec, gap_sec=label_gap_sec)
+                                      hints="auto" if auto else [hints[k] for k in idx], tol_sec=tol_sec,
+                                      gap_sec=label_gap_sec)
         except (ValueError, N.BpmxError) as exc:
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error

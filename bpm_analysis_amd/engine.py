@@ -690,6 +690,57 @@ class Scores:
         return out
 
 
+@dataclass
+class Tempo:
+    """bpmx_tempo_device's outputs for one batch (device tensors): per window
+    the lag, its strength and BPM (recording f's windows are
+    ``[woff[f], woff[f + 1])``), per recording the record.  ``hint`` is what
+    ``Detector.beats_device(hints=tempo)`` hands to the beat stages where it
+    lies."""
+    det: "object"
+    sr: int
+    win: int
+    hop: int
+    kmin: int
+    kmax: int
+    min_strength: float
+    start_windows: int
+    woff: np.ndarray             # [F + 1] int64, host
+    lag: "object"
+    rho: "object"
+    bpm: "object"
+    n_valid: "object"
+    n_strong: "object"
+    median_bpm: "object"
+    mean_rho: "object"
+    hint: "object"
+
+    @property
+    def n_files(self) -> int:
+        return len(self.woff) - 1
+
+    def to_host(self) -> List[dict]:
+        """Per recording the dict of ``tempo.tempogram``: ``time`` (the window
+        centres), ``lag``, ``rho``, ``bpm`` and the record."""
+        torch = _torch()
+        det = self.det
+        with det.lock:
+            t = {k: getattr(self, k).cpu().numpy() for k in ("lag", "rho", "bpm", "n_valid", "n_strong",
+                                                             "median_bpm", "mean_rho", "hint")}
+            torch.cuda.current_stream(det.device).synchronize()
+        out = []
+        for f in range(self.n_files):
+            a, b = int(self.woff[f]), int(self.woff[f + 1])
+            out.append(dict(sr=self.sr, win=self.win, hop=self.hop, kmin=self.kmin, kmax=self.kmax,
+                            min_strength=self.min_strength, start_windows=self.start_windows,
+                            time=(np.arange(b - a) * self.hop + self.win / 2) / self.sr,
+                            lag=t["lag"][a:b].copy(), rho=t["rho"][a:b].copy(), bpm=t["bpm"][a:b].copy(),
+                            n_valid=int(t["n_valid"][f]), n_strong=int(t["n_strong"][f]),
+                            median_bpm=float(t["median_bpm"][f]), mean_rho=float(t["mean_rho"][f]),
+                            hint=float(t["hint"][f])))
+        return out
+
+
 class Detector:
     """One libbpmx context on one GPU.
 
@@ -1201,7 +1252,9 @@ class Detector:
         Asynchronous; outputs are sized by ``packed.cap_peaks``.
 
         ``hints``: one start BPM per recording (None = no hint) in place of
-        `hint` for all of them, in the same launch.  ``trace``: the decision
+        `hint` for all of them, in the same launch, or the ``Tempo`` of
+        ``tempo_device``, whose device ``hint`` array the launch then reads
+        with no download.  ``trace``: the decision
         trace (``Beats.trace``; bpmx_beats_device_ex, kernel k_beats_trace)
         beside the same results, for ``Beats.to_host(explain=True)``."""
         from . import _host
@@ -1232,7 +1285,11 @@ class Detector:
         if not isinstance(params, _host.BeatParams):
             out.params = dict(params)
         d_hints = None
-        if hints is not None:
+        if isinstance(hints, Tempo):         # the tempo stage's hints, read where they lie
+            if hints.n_files != F:
+                raise N.BpmxError("beats_device: hints needs one entry per recording", N.E_ARG)
+            d_hints = hints.hint
+        elif hints is not None:
             if len(hints) != F:
                 raise N.BpmxError("beats_device: hints needs one entry per recording", N.E_ARG)
             hh = np.array([np.nan if h is None else float(h) for h in hints], dtype=np.float64)
@@ -1466,6 +1523,45 @@ class Detector:
                                              self.stream_handle()), "bpmx_marks_device")
         return out
 
+    def tempo_device(self, res: Result, params: Optional[dict] = None, win_sec: float = 8.0, hop_sec: float = 2.0,
+                     min_strength: float = 0.3, start_windows: int = 3,
+                     ints: Optional[Sequence[int]] = None) -> Tempo:
+        """bpmx_tempo_device on the current stream, behind the run that made
+        ``res.env``: the tempogram of every recording (``tempo.tempogram`` is
+        the same on the host), a BPM per window from the envelope's
+        autocorrelation and the record with the start hint.  The lag range is
+        ``max_bpm`` .. ``min_bpm`` of `params` (DEFAULT_PARAMS without);
+        ``ints``: (win, hop, kmin, kmax) in samples instead.  The defaults are
+        judgement, not measurement.  Asynchronous."""
+        from . import tempo as TP
+        torch = _torch()
+        if not hasattr(self.L, "bpmx_tempo_device"):
+            raise N.BpmxError("libbpmx.so has no bpmx_tempo_device; rebuild")
+        win, hop, kmin, kmax = [int(v) for v in (ints if ints is not None
+                                                 else TP.geometry(res.sr, params, win_sec, hop_sec))]
+        F, dev = res.n_files, self.device
+        woff = np.zeros(F + 1, np.int64)
+        woff[1:] = np.cumsum([TP.n_windows(int(res.doff[f + 1] - res.doff[f]), win, hop) for f in range(F)])
+        tot = int(woff[-1])
+        e = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)  # noqa: E731
+        out = Tempo(det=self, sr=int(res.sr), win=win, hop=hop, kmin=kmin, kmax=kmax,
+                    min_strength=float(min_strength), start_windows=int(start_windows), woff=woff,
+                    lag=e(tot, torch.int32), rho=e(tot, torch.float64), bpm=e(tot, torch.float64),
+                    n_valid=e(F, torch.int32), n_strong=e(F, torch.int32), median_bpm=e(F, torch.float64),
+                    mean_rho=e(F, torch.float64), hint=e(F, torch.float64))
+        p = N.TempoParams(win, hop, kmin, kmax, float(min_strength), int(start_windows), 0)
+        i = N.Out()
+        i.env = res.env.data_ptr()
+        o = N.TempoOut()
+        for name, _ in N.TempoOut._fields_:
+            setattr(o, name, getattr(out, name).data_ptr())
+        fo = res.frame_offsets
+        with self.lock:
+            N.check(self.L.bpmx_tempo_device(self.ctx, F, fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), res.ds,
+                                             int(res.sr), ctypes.byref(p), ctypes.byref(i), ctypes.byref(o),
+                                             self.stream_handle()), "bpmx_tempo_device")
+        return out
+
     def score_sweep(self, recordings: List[np.ndarray], fs: int, params_list: Sequence[dict],
                     ref_tables: Sequence[Optional[dict]], mode: str = "reference",
                     hints: Optional[Sequence[Optional[float]]] = None, tol_sec: float = 0.05, gap_sec: float = 5.0,
@@ -1477,7 +1573,9 @@ class Detector:
         ``beats_device(trace=True)``, ``labels_device`` and
         ``score_device(rows=False)``.  One download at the end returns
         ``(record [P, F, 20] int64, status [P, F] int32)`` in the caller's
-        order of recordings.  The settings must agree in ``downsample_factor``,
+        order of recordings.  ``hints="auto"``: ``tempo_device`` runs once on
+        the shared envelope (lag range of the first setting) and every setting's
+        beat stages read its hints on the device.  The settings must agree in ``downsample_factor``,
         the only key the envelope stage reads (ValueError otherwise, before
         anything runs).  Same lock, stream and longest-first rules as
         ``run_host_reports``."""
@@ -1490,7 +1588,10 @@ class Detector:
                              "is made with; sweep each value on its own")
         if len(ref_tables) != nF:
             raise ValueError("score_sweep: ref_tables needs one entry per recording")
-        hints = [None] * nF if hints is None else list(hints)
+        auto = isinstance(hints, str)
+        if auto and hints != "auto":
+            raise ValueError('score_sweep: hints is a sequence or "auto"')
+        hints = [None] * nF if hints is None or auto else list(hints)
         if len(hints) != nF:
             raise ValueError("score_sweep: hints needs one entry per recording")
         LB.score_ms(tol_sec, gap_sec)
@@ -1510,6 +1611,8 @@ class Detector:
             marks = self.upload_marks([ref_tables[i] for i in perm])
             res, _ = self._batch_on_device(recs, fs, params_list[0], mode, N.STAGE_ENVELOPE, False, False)
             ch = 1 if recs[0].ndim == 1 else recs[0].shape[1]
+            if auto:                             # once per sweep: the envelope is shared
+                hh = self.tempo_device(res, params_list[0])
             got = []
             for p, d in zip(params_list, designs):
                 self.run(None, res.frame_offsets, fs, p, mode=mode, stages=det_st, channels=ch, out=res, d=d)
@@ -1554,7 +1657,7 @@ class Detector:
     def run_host_reports(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                          hints: Optional[Sequence[Optional[float]]] = None, resolve_ties: bool = True,
                          longest_first: bool = True, plot: bool = False, labels: bool = False,
-                         label_gap_sec: float = 5.0) -> List[dict]:
+                         label_gap_sec: float = 5.0, tempo: bool = False) -> List[dict]:
         """Everything the reference's report set needs, with no classifier on
         the host: upload, run, ``resolve_ties``, ``pack`` (with the floor at
         the troughs, and the int16 debug samples when
@@ -1570,13 +1673,20 @@ class Detector:
         the reference), which ``plot.build_figure_packed`` takes.  With
         `labels`, each dict also carries ``labels`` (``labels_device`` at
         `label_gap_sec`, ``Labels.to_host``: the labeler's table, pairs, groups
-        and summary, or None where there are none).  Same lock,
+        and summary, or None where there are none).  ``hints="auto"``: the
+        tempo stage (``tempo_device``) runs on the envelope and the beat stages
+        read its hints on the device; each dict then carries
+        ``start_bpm_hint`` (the value used, None where there was none).  With
+        `tempo`, each dict carries ``tempo`` (``Tempo.to_host``).  Same lock,
         stream and longest-first rules as ``run_host_packed``."""
         torch = _torch()
         recordings = list(recordings)
         if not recordings:
             return []
-        hints = [None] * len(recordings) if hints is None else list(hints)
+        auto = isinstance(hints, str)
+        if auto and hints != "auto":
+            raise ValueError('run_host_reports: hints is a sequence or "auto"')
+        hints = [None] * len(recordings) if hints is None or auto else list(hints)
         if len(hints) != len(recordings):
             raise ValueError("run_host_reports: hints needs one entry per recording")
         perm = list(range(len(recordings)))
@@ -1590,11 +1700,15 @@ class Detector:
             pk = self.pack(res, d.distance, want_y16=y16, want_tr_floor=True)
             if plot:
                 ps = self.pack_plot(res, plot_device_factor(params.get("plot_downsample_factor", 5)))
-            b = self.beats_device(pk, params, hints=hh, trace=True)
+            if auto or tempo:
+                tp = self.tempo_device(res, params)
+            b = self.beats_device(pk, params, hints=tp if auto else hh, trace=True)
             met = self.metrics_device(b, params)
             if labels:
                 lab = self.labels_device(b, label_gap_sec)
             got = met.to_host(explain=True)
+            if auto or tempo:
+                tps = tp.to_host()
             if labels:
                 labs = lab.to_host()
             tabs = pk.to_host()
@@ -1606,6 +1720,11 @@ class Detector:
             out[i] = dict(tabs[k], **got[k])
             if labels:
                 out[i]["labels"] = labs[k]
+            if auto:
+                h = tps[k]["hint"]
+                out[i]["start_bpm_hint"] = None if h != h else h
+            if tempo:
+                out[i]["tempo"] = tps[k]
             if plot:
                 if tabs[k]["flags"] & N.F_TOO_SHORT:    # no outputs: empty series, not the buffers' old contents
                     series[k]["env_plot"], series[k]["floor_plot"] = np.zeros(0), np.zeros(0)

@@ -55,7 +55,7 @@ extern "C" {
 /* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
  * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL;
  * bpmx_score_device and BPMX_OPT_SCORE_GLOBAL; bpmx_marks_device and
- * BPMX_OPT_MARKS_GLOBAL; BPMX_DT_I24. */
+ * BPMX_OPT_MARKS_GLOBAL; BPMX_DT_I24; bpmx_tempo_windows and bpmx_tempo_device. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
@@ -781,6 +781,74 @@ enum bpmx_marks_record {        /* record: 8 int32 per file */
 int bpmx_marks_device(bpmx_ctx *ctx, int32_t n_files, int32_t sr, const bpmx_marks_params *params,
                       const bpmx_ref_marks *marks, const int64_t *nd, const bpmx_packed *tables,
                       const bpmx_beats_out *beats, int32_t *gap, int32_t *record, void *stream);
+
+/* The tempogram on the device (bpmx_tempo_device).
+ *
+ * A BPM per window from the short-time autocorrelation of the envelope, which
+ * uses neither find_peaks nor the classifier: a second opinion on the BPM
+ * curve (an octave error shows as a factor of two) and, from the first
+ * windows, a start hint per recording that bpmx_beats_device_ex reads where it
+ * lies.  The reference has no such stage; this is the definition
+ * (csrc/bpmx_tempo_core.h states the decisions for host and device,
+ * tempo.tempogram in Python the whole of it).
+ *
+ *   Windows: window w of a recording of nd envelope samples starts at s = w *
+ *       hop; there are bpmx_tempo_windows(nd, win, hop) = 0 if nd < win, else
+ *       (nd - win) / hop + 1 of them.
+ *   Per window: invalid if any of its win samples is not finite or if
+ *       max == min.  Else m = sum / win, e[i] = x[s + i] - m for i < win and 0
+ *       beyond, r[k] = sum_{i < win} e[i] * e[i + k] for k = kmin - 1 .. kmax + 1
+ *       and k = 0.  The candidates are the k in [kmin, kmax] with r[k] > r[k - 1]
+ *       and r[k] >= r[k + 1]; none: invalid.  The lag is the candidate of the
+ *       largest r[k], the smallest k among equals.  rho = r[k] / r[0],
+ *       delta = 0.5 * (r[k - 1] - r[k + 1]) / (r[k - 1] - 2 * r[k] + r[k + 1]),
+ *       bpm = 60.0 * sr / (k + delta).  An invalid window has lag 0, rho 0.0,
+ *       bpm NaN.
+ *   Per recording: n_valid counts the valid windows, n_strong the strong ones
+ *       (valid and rho >= min_strength); median_bpm is numpy's median of the
+ *       strong windows' bpm and mean_rho the mean of rho over the valid windows
+ *       (NaN with none); hint is the bpm of the first strong window among the
+ *       windows 0 .. start_windows - 1, NaN with none: what
+ *       bpmx_beats_device_ex reads as "no hint".
+ *
+ * The sums are f64 in an order of the kernel's own (products fused into the
+ * running sums): rho agrees with another order of summation to about
+ * win * 2^-52 * (1 + (m / sigma)^2), so a decision between lags closer than
+ * that may differ.  min_strength and start_windows are judgement (0.3 and 3 in
+ * the Python layer), not measurement.
+ *
+ * Limits: hop >= 1, kmin >= 2, kmin <= kmax and kmax + 1 < win, else BPMX_E_ARG.
+ * A workgroup keeps the padded window and four partial sums per lag in LDS:
+ * with win4 = win rounded up to a multiple of 4,
+ *   8 * (win4 + kmax + 8 + 4 * (kmax - kmin + 4)) <= 155648 bytes (152 KB),
+ * else BPMX_E_LIMIT.  That is 8 s windows down to 30 BPM at rates up to about
+ * 1 kHz; envelopes at audio rates are not the target. */
+typedef struct {
+    int32_t win, hop;           /* window and step, samples */
+    int32_t kmin, kmax;         /* lag range, samples: ceil(60 sr / max_bpm), floor(60 sr / min_bpm) */
+    double min_strength;        /* a window is strong when rho >= this */
+    int32_t start_windows;      /* the hint comes from the first this many windows */
+    int32_t reserved;           /* 0 */
+} bpmx_tempo_params;
+
+typedef struct {            /* device */
+    int32_t *lag;               /* per window; a file's slice starts at the sum of the windows before it */
+    double *rho, *bpm;          /* per window */
+    int32_t *n_valid, *n_strong;            /* [n_files] */
+    double *median_bpm, *mean_rho, *hint;   /* [n_files] */
+} bpmx_tempo_out;
+
+int64_t bpmx_tempo_windows(int64_t nd, int32_t win, int32_t hop);
+
+/* The tempogram of n_files recordings at rate sr from their envelopes in->env
+ * (per-file slices at the decimated offsets of frame_offsets and ds, as for
+ * bpmx_pack; nothing else of `in` is read), asynchronously on `stream`, ordered
+ * after the run.  Every pointer of `out` is required.  Nothing beyond the
+ * window total of the per-window arrays is written.  Never synchronises the
+ * host; scratch comes from ctx.  n_files = 0 does nothing.  Two launches: one
+ * workgroup per window, one wave per recording; see csrc/k_tempo.hip. */
+int bpmx_tempo_device(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t sr,
+                      const bpmx_tempo_params *params, const bpmx_out *in, const bpmx_tempo_out *out, void *stream);
 
 /* bpmx_option bits for the entry points that take no bpmx_params
  * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL, BPMX_OPT_SCORE_GLOBAL,
