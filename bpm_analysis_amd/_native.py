@@ -44,6 +44,7 @@ OPT_LABELS_GLOBAL = 131072          # bpmx_labels_device, through bpmx_set_optio
 OPT_SCORE_GLOBAL = 262144           # bpmx_score_device, through bpmx_set_options (test/diagnostic)
 OPT_MARKS_GLOBAL = 524288           # bpmx_marks_device, through bpmx_set_options (test/diagnostic)
 OPT_FLOOR_ONEWG = 1048576           # the floor by one workgroup per recording, not two halves (test/diagnostic)
+OPT_HRVSPEC_DIRECT = 2097152        # bpmx_hrvspec_device: one sincos per term, no rotation along the grid (test/diagnostic)
 STAT_RAW_TROUGHS, STAT_UNDECIDED, STAT_FULL_DRAFT, NSTATS = 0, 1, 2, 8
 STAT_FLOOR_WHOLE = 3                # recordings the half-recording floor launch handed to the whole-recording one
 OK, E_ARG, E_HIP, E_LIMIT, E_NODEV = 0, -1, -2, -3, -4
@@ -78,7 +79,7 @@ EXPORTS = ["bpmx_abi_version", "bpmx_last_error", "bpmx_create", "bpmx_destroy",
            "bpmx_stats", "bpmx_set_pipeline", "bpmx_beats_device", "bpmx_set_options", "bpmx_metrics_device",
            "bpmx_beats_device_ex", "bpmx_pack_trough_floor", "bpmx_plot_length", "bpmx_pack_plot",
            "bpmx_labels_device", "bpmx_score_device", "bpmx_marks_device", "bpmx_tempo_windows",
-           "bpmx_tempo_device"]
+           "bpmx_tempo_device", "bpmx_hrvspec_windows", "bpmx_hrvspec_device"]
 
 
 class Params(ctypes.Structure):
@@ -207,6 +208,31 @@ class TempoOut(ctypes.Structure):
                                                "hint")]
 
 
+class HrvspecParams(ctypes.Structure):
+    """bpmx_hrvspec_params: window, step, interval range, validity limits, the
+    frequency grid and the two bands as index ranges on it."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("win", "hop", "dmin", "dmax", "min_intervals", "min_span", "n_freq",
+                                              "lf_a", "lf_b", "hf_a", "hf_b", "reserved")] + \
+               [(k, ctypes.c_double) for k in ("om0", "dom", "scale")]
+
+
+class HrvspecOut(ctypes.Structure):
+    """bpmx_hrvspec_out: the device arrays bpmx_hrvspec_device fills (per
+    window, then per file; q is optional)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("code", "n_rr", "lf_peak", "hf_peak", "t_mid", "var", "lf", "hf", "q",
+                                               "record", "status")]
+
+
+HRVSPEC_OK, HRVSPEC_NONE, HRVSPEC_OVERFLOW, HRVSPEC_RECORD = 0, -26, -27, 8
+
+
+def hrvspec_params(g: dict) -> HrvspecParams:
+    """``hrv_spectrum.geometry``'s dict as the structure."""
+    return HrvspecParams(*[int(g[k]) for k in ("win", "hop", "dmin", "dmax", "min_intervals", "min_span", "n_freq",
+                                               "lf_a", "lf_b", "hf_a", "hf_b")], 0,
+                         float(g["om0"]), float(g["dom"]), float(g["scale"]))
+
+
 class BpmxError(RuntimeError):
     """A libbpmx failure.  ``code`` is the BPMX_E_* status (None when raised by
     the host side).  Only argument and size-limit errors belong to the
@@ -316,6 +342,13 @@ def load() -> ctypes.CDLL:
         L.bpmx_tempo_device.argtypes = [P, I32, ctypes.POINTER(ctypes.c_int64), I32, I32,
                                         ctypes.POINTER(TempoParams), ctypes.POINTER(Out), ctypes.POINTER(TempoOut), P]
         L.bpmx_tempo_device.restype = ctypes.c_int
+    if hasattr(L, "bpmx_hrvspec_device"):
+        L.bpmx_hrvspec_windows.argtypes = [I64, I32, I32]
+        L.bpmx_hrvspec_windows.restype = I64
+        L.bpmx_hrvspec_device.argtypes = [P, I32, ctypes.POINTER(ctypes.c_int64), I32, I32,
+                                          ctypes.POINTER(HrvspecParams), ctypes.POINTER(PackedOut),
+                                          ctypes.POINTER(BeatsOut), ctypes.POINTER(HrvspecOut), P]
+        L.bpmx_hrvspec_device.restype = ctypes.c_int
     if L.bpmx_abi_version() != ABI_VERSION:
         raise BpmxError(f"libbpmx ABI {L.bpmx_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

@@ -3,7 +3,8 @@
  * synthetic input, per-kernel event timing, the pipelined run, bpmx_pack,
  * bpmx_pack_trough_floor, bpmx_pack_plot, bpmx_beats_device,
  * bpmx_beats_device_ex, bpmx_metrics_device, bpmx_labels_device,
- * bpmx_score_device, bpmx_marks_device and bpmx_tempo_device.
+ * bpmx_score_device, bpmx_marks_device, bpmx_tempo_device and
+ * bpmx_hrvspec_device.
  * A run's stages are sequenced by bpmx_run.hip (run_impl).
  */
 #include <hip/hip_runtime.h>
@@ -870,6 +871,67 @@ int bpmx_tempo_device(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offse
         }
     }
     LAUNCH(ctx, s, "k_tempo_record", k_tempo_record, dim3((unsigned)n_files), dim3(TEMPO_REC_T), 0, s, a);
+    return BPMX_OK;
+}
+
+int64_t bpmx_hrvspec_windows(int64_t nd, int32_t win, int32_t hop) { return hrvspec_windows(nd, win, hop); }
+
+int bpmx_hrvspec_device(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t sr,
+                        const bpmx_hrvspec_params *params, const bpmx_packed *tables, const bpmx_beats_out *beats,
+                        const bpmx_hrvspec_out *out, void *stream) {
+    if (!ctx || !frame_offsets || !params || !tables || !beats || !out)
+        return fail(BPMX_E_ARG, "bpmx_hrvspec_device: NULL argument");
+    if (n_files < 0 || ds < 1 || sr < 1) return fail(BPMX_E_ARG, "bpmx_hrvspec_device: bad n_files/ds/sr");
+    const HrvspecPlan G = hrvspec_plan(*params);
+    if (G.status == BPMX_E_ARG)
+        return fail(BPMX_E_ARG, "bpmx_hrvspec_device: needs hop >= 1, 1 <= dmin <= dmax, min_intervals >= 3, "
+                                "1 <= n_freq <= 1024, 0 <= a <= b <= n_freq for both bands, om0 and dom finite, "
+                                "om0 > 0 and dom >= 0");
+    if (G.status != BPMX_OK)
+        return fail(BPMX_E_LIMIT, "bpmx_hrvspec_device: a window's intervals exceed a workgroup's LDS "
+                                  "(32 * (win / dmin + 1) > " + std::to_string((int)HRVSPEC_LDS_MAX) + " bytes)");
+    if (n_files == 0) return BPMX_OK;
+    if (!tables->pk_off || tables->cap_peaks < 0 || tables->cap_peaks >= (int64_t)INT_MAX)
+        return fail(BPMX_E_ARG, "bpmx_hrvspec_device: needs pk_off and 0 <= cap_peaks < 2^31");
+    if (!beats->final_idx || !beats->n_final || !beats->status)
+        return fail(BPMX_E_ARG, "bpmx_hrvspec_device: the beats' final_idx, n_final and status are required");
+    if (!out->code || !out->n_rr || !out->lf_peak || !out->hf_peak || !out->t_mid || !out->var || !out->lf ||
+        !out->hf || !out->record || !out->status)
+        return fail(BPMX_E_ARG, "bpmx_hrvspec_device: every pointer of bpmx_hrvspec_out but q is required");
+    const size_t F = (size_t)n_files;
+    std::vector<int64_t> geo(F + 1);
+    geo[0] = 0;
+    for (size_t f = 0; f < F; ++f) {
+        const int64_t n = frame_offsets[f + 1] - frame_offsets[f];
+        if (n < 0) return fail(BPMX_E_ARG, "frame offsets must be non-decreasing");
+        const int64_t nd = bpmx_decimated_length(n, ds);
+        if (nd >= (int64_t)INT_MAX / 2) return fail(BPMX_E_LIMIT, "recording too long");
+        geo[f + 1] = geo[f] + hrvspec_windows(nd, params->win, params->hop);
+    }
+    const int64_t total = geo[F];
+    if (total >= (int64_t)INT_MAX) return fail(BPMX_E_LIMIT, "bpmx_hrvspec_device: too many windows");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = BPMX_OK;
+    bool grew = false;
+    int64_t *d_geo = (int64_t *)ctx->buf("hrvspec_geo", geo.size() * 8, &rc, &grew);
+    if (rc != BPMX_OK) return rc;
+    if (grew || geo != ctx->hrvspec_key) {
+        /* stream-ordered: launches of an earlier call still read the old geometry */
+        ctx->hrvspec_key.swap(geo);
+        HIP_TRY(hipMemcpyAsync(d_geo, ctx->hrvspec_key.data(), ctx->hrvspec_key.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    HrvspecArgs a{};
+    a.n_files = n_files; a.sr = sr; a.cap = tables->cap_peaks; a.P = *params; a.G = G;
+    a.woff = d_geo; a.pk_off = tables->pk_off;
+    a.final_idx = beats->final_idx; a.n_final = beats->n_final; a.b_status = beats->status; a.O = *out;
+    if (total > 0) {
+        if (ctx->options & BPMX_OPT_HRVSPEC_DIRECT)
+            LAUNCH(ctx, s, "k_hrvspec_direct", (k_hrvspec<1, 1, false>), dim3((unsigned)total), dim3(HRVSPEC_T), G.lds, s, a);
+        else
+            LAUNCH(ctx, s, "k_hrvspec", (k_hrvspec<HRVSPEC_B, HRVSPEC_PARTS, true>), dim3((unsigned)total), dim3(HRVSPEC_T), G.lds, s, a);
+    }
+    LAUNCH(ctx, s, "k_hrvspec_record", k_hrvspec_record, dim3((unsigned)n_files), dim3(HRVSPEC_REC_T), 0, s, a);
     return BPMX_OK;
 }
 

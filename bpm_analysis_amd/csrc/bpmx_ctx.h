@@ -40,6 +40,7 @@ struct bpmx_ctx {
     std::vector<int64_t> pack_key; /* decimated offsets in "pack_geo" (bpmx_pack; also the upload's host source) */
     std::vector<int64_t> plot_key; /* geometry in "plot_geo" (bpmx_pack_plot; also the upload's host source) */
     std::vector<int64_t> tempo_key; /* envelope and window offsets in "tempo_geo" (bpmx_tempo_device; also the upload's host source) */
+    std::vector<int64_t> hrvspec_key; /* window offsets in "hrvspec_geo" (bpmx_hrvspec_device; also the upload's host source) */
     /* native-mode block-state tables (host copies back the async uploads) */
     std::vector<int64_t> nat_key;
     std::vector<double> nat_tab;

@@ -6,6 +6,7 @@
 
 #include "bpmx_common.h"
 #include "bpmx_tempo_core.h"
+#include "bpmx_hrvspec_core.h"
 
 namespace bpmx {
 
@@ -708,6 +709,22 @@ struct TempoArgs {
 template <int L>
 __global__ void k_tempo_valu(TempoArgs A);
 __global__ void k_tempo_record(TempoArgs A);
+
+/* bpmx_hrvspec_device (k_hrvspec.hip): one workgroup of HRVSPEC_T threads per
+ * (recording, window) pair, then one wave per recording for the record */
+struct HrvspecArgs {
+    int32_t n_files, sr;
+    int64_t cap;                /* table capacity, entries */
+    bpmx_hrvspec_params P;
+    HrvspecPlan G;              /* bpmx_hrvspec_core.h hrvspec_plan */
+    const int64_t *woff;        /* [F+1] window offsets: the prefix sums of bpmx_hrvspec_windows */
+    const int64_t *pk_off;      /* [F+1] */
+    const int32_t *final_idx, *n_final, *b_status;   /* the beat stages' outputs */
+    bpmx_hrvspec_out O;
+};
+template <int B, int PARTS, bool ROT>
+__global__ void k_hrvspec(HrvspecArgs A);
+__global__ void k_hrvspec_record(HrvspecArgs A);
 
 /* Rectified-mode envelope (k_rect.hip): the centred rolling mean of |x| at the
  * native rate.  Integer PCM of one or two channels takes the exact-integer

@@ -332,7 +332,8 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                                  start_bpm_hints: Sequence = None, original_file_paths: Sequence[str] = None,
                                  mode: str = None, device: int = 0, plot: bool = False, labels: bool = False,
                                  label_gap_sec: float = 5.0, labels_overwrite: bool = False,
-                                 packed24: bool = False, tempo: bool = False) -> List[dict]:
+                                 packed24: bool = False, tempo: bool = False,
+                                 hrv_spectrum: bool = False) -> List[dict]:
     """``beats.analyze_wav_file`` for many WAV files with every stage on the
     device: per file ``<base>_bpm_plot.csv``, ``<base>_Analysis_Summary.md``,
     ``<base>_Debug_Log.md`` and ``<base>_Analysis_Settings.json`` (and both
@@ -378,6 +379,14 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     reports (``tempo.write_csv``).  With neither, the stage does not run and
     every byte written is as before.
 
+    ``hrv_spectrum=True``: the HRV spectrum (``Detector.hrv_spectrum_device``:
+    per 120 s window, every 30 s, the Lomb-Scargle periodogram of the RR
+    intervals, LF and HF power and the band peaks) runs on the device behind
+    the beat stages; each dict gains ``hrv_spectrum``
+    (``hrv_spectrum.spectrum``'s dict) and ``<base>_hrv_spectrum.csv`` is
+    written beside the reports (``hrv_spectrum.write_csv``).  Left false, the
+    stage does not run and every byte written is as before.
+
     Returns one dict per path, in order: ``run_host_reports``' dict, or
     ``error`` with the exception the reference raises for that file; as there,
     a file with fewer than two final beats gets no reports
@@ -386,6 +395,7 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
     from .reports import write_reports_packed
     from . import labels as LB
     from . import tempo as TP
+    from . import hrv_spectrum as HS
     if mode is None:
         mode = params.get("bpmx_mode", "reference")
     n = len(file_paths)
@@ -428,7 +438,8 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
             res = det.run_host_reports([audio[k][1] for k in idx], fs, run_params, mode=mode,
                                        hints="auto" if auto else [hints[k] for k in idx], plot=plot,
                                        **(dict(labels=True, label_gap_sec=label_gap_sec) if labels else {}),
-                                       **(dict(tempo=True) if tempo else {}))
+                                       **(dict(tempo=True) if tempo else {}),
+                                       **(dict(hrv_spectrum=True) if hrv_spectrum else {}))
         except (ValueError, N.BpmxError) as exc:      # reported per file, as the GUI loop does (gui.py:247-251)
             if isinstance(exc, N.BpmxError) and not exc.per_file:
                 raise                                 # HIP / device failure: not a per-file error
@@ -458,6 +469,8 @@ def analyze_wav_files_to_reports(file_paths: Sequence[str], params: Dict, output
                 write_reports_packed(names[k], output_directory, r, hints[k])
                 if tempo:
                     TP.write_csv(TP.tempo_path(names[k], output_directory), r["tempo"], r["tempo_check"])
+                if hrv_spectrum:
+                    HS.write_csv(HS.spectrum_path(names[k], output_directory), r["hrv_spectrum"])
                 if labels and r["labels"] is not None:
                     r["labels_written"] = LB.write_labels(LB.labels_path(names[k], output_directory), r["labels"],
                                                           overwrite=labels_overwrite)
@@ -597,7 +610,7 @@ def _read_marks(path: str, rate):
 def revise_from_labels(label_paths: Sequence[str], sample_rates=None, params: Dict = None,
                        output_directory: str = None, gap_sec: float = 5.0, suffix: str = "_corrected",
                        overwrite: bool = False, device: int = 0, wav_paths: Sequence[str] = None,
-                       mode: str = None) -> List[dict]:
+                       mode: str = None, hrv_spectrum: bool = False) -> List[dict]:
     """The analysis of a person's own marks: every corrected
     ``<base>_labels.csv`` goes through ``Detector.marks_device``,
     ``metrics_device`` and ``labels_device``, so the BPM curve, the HRV table,
@@ -618,8 +631,15 @@ def revise_from_labels(label_paths: Sequence[str], sample_rates=None, params: Di
     ``<base><suffix>_Analysis_Summary.md``, ``<base><suffix>_bpm_plot.csv``
     and ``<base><suffix>_labels.csv`` (``written``: the paths), where <base> is
     the label file's name without ``_labels.csv``; an existing file is left as
-    it is unless `overwrite` (``skipped``: those paths)."""
+    it is unless `overwrite` (``skipped``: those paths).
+
+    ``hrv_spectrum=True``: the HRV spectrum follows the corrected beats
+    (``Detector.hrv_spectrum_device`` behind ``marks_device``); a label file
+    carries no recording length, so the recording is taken to end one sample
+    after its last mark.  Each dict gains ``hrv_spectrum``, and
+    ``<base><suffix>_hrv_spectrum.csv`` is written with the others."""
     from . import beats as B
+    from . import hrv_spectrum as HS
     from . import labels as LB
     from . import reports as R
     params = dict(DEFAULT_PARAMS if params is None else params)
@@ -643,9 +663,14 @@ def revise_from_labels(label_paths: Sequence[str], sample_rates=None, params: Di
             beats = det.marks_device([marks[k] for k in idx], sr, params)
             res = det.metrics_device(beats, params).to_host()
             labs = det.labels_device(beats, gap_sec).to_host()
+            if hrv_spectrum:
+                ends = [(int(max(marks[k]["ms"], default=-1)) * sr + 500) // 1000 + 1 for k in idx]
+                specs = det.hrv_spectrum_device(beats, lengths=ends, params=params).to_host()
             det.host_stream().synchronize()
-        for k, r, lab in zip(idx, res, labs):
+        for j, (k, r, lab) in enumerate(zip(idx, res, labs)):
             r = dict(r, labels=lab, sr=sr)
+            if hrv_spectrum:
+                r["hrv_spectrum"] = specs[j]
             out[k] = r
             if output_directory is None:
                 continue
@@ -658,6 +683,8 @@ def revise_from_labels(label_paths: Sequence[str], sample_rates=None, params: Di
             jobs = ((f"{base}_Analysis_Summary.md", lambda p: _write_text(p, R.summary_text(base, m))),
                     (f"{base}_bpm_plot.csv", lambda p: B.write_bpm_csv(p, m)),
                     (f"{base}_labels.csv", lambda p: lab is not None and LB.write_labels(p, lab, overwrite=True)))
+            if hrv_spectrum:
+                jobs += ((f"{base}_hrv_spectrum.csv", lambda p: HS.write_csv(p, r["hrv_spectrum"]) is None),)
             for fname, write in jobs:
                 p = os.path.join(output_directory, fname)
                 if os.path.exists(p) and not overwrite:

@@ -741,6 +741,64 @@ class Tempo:
         return out
 
 
+@dataclass
+class HrvSpectrum:
+    """bpmx_hrvspec_device's outputs for one batch (device tensors): per window
+    the code, the interval count, the centre time, the variance, LF and HF
+    power and the band peaks (recording f's windows are
+    ``[woff[f], woff[f + 1])``), optionally the rows of ``q``, per recording the
+    8-double record and a status."""
+    det: "object"
+    beats: "object"
+    sr: int
+    g: dict                      # hrv_spectrum.geometry's dict
+    lengths: np.ndarray          # [F] int64 envelope lengths, host
+    woff: np.ndarray             # [F + 1] int64, host
+    code: "object"
+    n_rr: "object"
+    lf_peak: "object"
+    hf_peak: "object"
+    t_mid: "object"
+    var: "object"
+    lf: "object"
+    hf: "object"
+    q: "object"                  # None without want_q
+    record: "object"
+    status: "object"
+
+    @property
+    def n_files(self) -> int:
+        return len(self.woff) - 1
+
+    def to_host(self) -> List[dict]:
+        """Per recording the dict of ``hrv_spectrum.spectrum``: the settings,
+        ``time``, ``n_rr``, ``code``, ``var``, ``lf``, ``hf``, ``lf_peak``,
+        ``hf_peak`` (``q`` with want_q), ``record`` and ``status``.  Raises
+        BpmxError (E_LIMIT) when the peak table was too small."""
+        torch = _torch()
+        det = self.det
+        names = ["code", "n_rr", "lf_peak", "hf_peak", "t_mid", "var", "lf", "hf", "record", "status"]
+        if self.q is not None:
+            names.append("q")
+        with det.lock:
+            t = {k: getattr(self, k).cpu().numpy() for k in names}
+            torch.cuda.current_stream(det.device).synchronize()
+        if (t["status"][:self.n_files] == N.HRVSPEC_OVERFLOW).any():
+            raise N.BpmxError("packed tables too small for the beats' slices", N.E_LIMIT)
+        nq = self.g["n_freq"]
+        out = []
+        for f in range(self.n_files):
+            a, b = int(self.woff[f]), int(self.woff[f + 1])
+            d = dict(self.g, sr=self.sr, status=int(t["status"][f]), time=t["t_mid"][a:b].copy(),
+                     record=t["record"][f * N.HRVSPEC_RECORD:(f + 1) * N.HRVSPEC_RECORD].copy())
+            for k in ("n_rr", "code", "var", "lf", "hf", "lf_peak", "hf_peak"):
+                d[k] = t[k][a:b].copy()
+            if self.q is not None:
+                d["q"] = t["q"][a * nq:b * nq].reshape(b - a, nq).copy()
+            out.append(d)
+        return out
+
+
 class Detector:
     """One libbpmx context on one GPU.
 
@@ -1312,7 +1370,7 @@ class Detector:
 
     def set_options(self, options: int) -> None:
         """Context-level option bits (N.OPT_BEATS_GLOBAL, N.OPT_METRICS_GLOBAL, N.OPT_LABELS_GLOBAL,
-        N.OPT_SCORE_GLOBAL, N.OPT_MARKS_GLOBAL; test/diagnostic)."""
+        N.OPT_SCORE_GLOBAL, N.OPT_MARKS_GLOBAL, N.OPT_HRVSPEC_DIRECT; test/diagnostic)."""
         with self.lock:
             N.check(self.L.bpmx_set_options(self.ctx, int(options)), "bpmx_set_options")
 
@@ -1562,6 +1620,65 @@ class Detector:
                                              self.stream_handle()), "bpmx_tempo_device")
         return out
 
+    def hrv_spectrum_device(self, beats: Beats, lengths: Optional[Sequence[int]] = None,
+                            params: Optional[dict] = None, want_q: bool = False, g: Optional[dict] = None,
+                            **kw) -> HrvSpectrum:
+        """bpmx_hrvspec_device on the current stream, behind the
+        ``beats_device`` or ``marks_device`` that filled `beats`: per window of
+        every recording the Lomb-Scargle periodogram of its RR intervals, LF
+        and HF power and the band peaks (``hrv_spectrum.spectrum`` is the same
+        on the host).  ``lengths``: the recordings' envelope lengths in samples
+        at the beats' rate; they default to those of the run behind
+        ``beats.packed`` and are required for beats that came from
+        ``marks_device`` (ValueError otherwise).  The interval range is
+        ``max_bpm`` .. ``min_bpm`` of `params` (DEFAULT_PARAMS without); `kw`:
+        the other arguments of ``hrv_spectrum.geometry`` (windows of 120 s
+        every 30 s, 16 intervals, 256 frequencies from 0.04 to 0.40 Hz, LF up to
+        0.15 Hz: judgement, not measurement); ``g``: its dict instead.
+        ``want_q``: the rows of q as well.  Asynchronous."""
+        from . import hrv_spectrum as HS
+        torch = _torch()
+        if not hasattr(self.L, "bpmx_hrvspec_device"):
+            raise N.BpmxError("libbpmx.so has no bpmx_hrvspec_device; rebuild")
+        packed = beats.packed
+        F, dev, sr = packed.n_files, self.device, int(packed.sr)
+        if lengths is None:
+            if beats.marks is not None:
+                raise ValueError("hrv_spectrum_device: beats from marks_device carry no recording lengths; "
+                                 "pass lengths")
+            lengths = np.diff(np.asarray(packed.doff, dtype=np.int64))
+        lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+        if len(lengths) != F:
+            raise ValueError("hrv_spectrum_device: lengths needs one entry per recording")
+        g = dict(HS.geometry(sr, params, **kw) if g is None else g)
+        HS.check_geometry(g)
+        fo = np.zeros(F + 1, np.int64)
+        fo[1:] = np.cumsum(lengths)
+        woff = np.zeros(F + 1, np.int64)
+        woff[1:] = np.cumsum([HS.n_windows(int(n), g["win"], g["hop"]) for n in lengths])
+        tot = int(woff[-1])
+        e = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)  # noqa: E731
+        out = HrvSpectrum(det=self, beats=beats, sr=sr, g=g, lengths=lengths, woff=woff,
+                          code=e(tot, torch.int32), n_rr=e(tot, torch.int32), lf_peak=e(tot, torch.int32),
+                          hf_peak=e(tot, torch.int32), t_mid=e(tot, torch.float64), var=e(tot, torch.float64),
+                          lf=e(tot, torch.float64), hf=e(tot, torch.float64),
+                          q=e(tot * g["n_freq"], torch.float64) if want_q else None,
+                          record=e(F * N.HRVSPEC_RECORD, torch.float64), status=e(F, torch.int32))
+        k = N.PackedOut()
+        k.cap_peaks, k.pk_off = packed.cap_peaks, packed.pk_off.data_ptr()
+        b = N.BeatsOut()
+        b.final_idx, b.n_final, b.status = beats.final_idx.data_ptr(), beats.n_final.data_ptr(), beats.status.data_ptr()
+        o = N.HrvspecOut()
+        for name, _ in N.HrvspecOut._fields_:
+            v = getattr(out, name)
+            setattr(o, name, None if v is None else v.data_ptr())
+        p = N.hrvspec_params(g)
+        with self.lock:
+            N.check(self.L.bpmx_hrvspec_device(self.ctx, F, fo.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 1, sr,
+                                               ctypes.byref(p), ctypes.byref(k), ctypes.byref(b), ctypes.byref(o),
+                                               self.stream_handle()), "bpmx_hrvspec_device")
+        return out
+
     def score_sweep(self, recordings: List[np.ndarray], fs: int, params_list: Sequence[dict],
                     ref_tables: Sequence[Optional[dict]], mode: str = "reference",
                     hints: Optional[Sequence[Optional[float]]] = None, tol_sec: float = 0.05, gap_sec: float = 5.0,
@@ -1657,7 +1774,8 @@ class Detector:
     def run_host_reports(self, recordings: List[np.ndarray], fs: int, params: dict, mode: str = "reference",
                          hints: Optional[Sequence[Optional[float]]] = None, resolve_ties: bool = True,
                          longest_first: bool = True, plot: bool = False, labels: bool = False,
-                         label_gap_sec: float = 5.0, tempo: bool = False) -> List[dict]:
+                         label_gap_sec: float = 5.0, tempo: bool = False,
+                         hrv_spectrum: bool = False) -> List[dict]:
         """Everything the reference's report set needs, with no classifier on
         the host: upload, run, ``resolve_ties``, ``pack`` (with the floor at
         the troughs, and the int16 debug samples when
@@ -1677,8 +1795,10 @@ class Detector:
         tempo stage (``tempo_device``) runs on the envelope and the beat stages
         read its hints on the device; each dict then carries
         ``start_bpm_hint`` (the value used, None where there was none).  With
-        `tempo`, each dict carries ``tempo`` (``Tempo.to_host``).  Same lock,
-        stream and longest-first rules as ``run_host_packed``."""
+        `tempo`, each dict carries ``tempo`` (``Tempo.to_host``).  With
+        `hrv_spectrum`, each dict carries ``hrv_spectrum``
+        (``hrv_spectrum_device`` at its defaults, ``HrvSpectrum.to_host``).
+        Same lock, stream and longest-first rules as ``run_host_packed``."""
         torch = _torch()
         recordings = list(recordings)
         if not recordings:
@@ -1706,9 +1826,13 @@ class Detector:
             met = self.metrics_device(b, params)
             if labels:
                 lab = self.labels_device(b, label_gap_sec)
+            if hrv_spectrum:
+                hs = self.hrv_spectrum_device(b, params=params)
             got = met.to_host(explain=True)
             if auto or tempo:
                 tps = tp.to_host()
+            if hrv_spectrum:
+                hss = hs.to_host()
             if labels:
                 labs = lab.to_host()
             tabs = pk.to_host()
@@ -1725,6 +1849,8 @@ class Detector:
                 out[i]["start_bpm_hint"] = None if h != h else h
             if tempo:
                 out[i]["tempo"] = tps[k]
+            if hrv_spectrum:
+                out[i]["hrv_spectrum"] = hss[k]
             if plot:
                 if tabs[k]["flags"] & N.F_TOO_SHORT:    # no outputs: empty series, not the buffers' old contents
                     series[k]["env_plot"], series[k]["floor_plot"] = np.zeros(0), np.zeros(0)

@@ -55,7 +55,8 @@ extern "C" {
 /* Added within version 4 (no existing call changes): BPMX_MODE_RECTIFIED and
  * BPMX_OPT_RECT_SEQ; bpmx_labels_device and BPMX_OPT_LABELS_GLOBAL;
  * bpmx_score_device and BPMX_OPT_SCORE_GLOBAL; bpmx_marks_device and
- * BPMX_OPT_MARKS_GLOBAL; BPMX_DT_I24; bpmx_tempo_windows and bpmx_tempo_device. */
+ * BPMX_OPT_MARKS_GLOBAL; BPMX_DT_I24; bpmx_tempo_windows and bpmx_tempo_device;
+ * bpmx_hrvspec_windows, bpmx_hrvspec_device and BPMX_OPT_HRVSPEC_DIRECT. */
 #define BPMX_ABI_VERSION 4
 
 /* sample formats of scipy.io.wavfile.read (bpm_analysis.py:1014) */
@@ -182,10 +183,13 @@ enum bpmx_option {
                                         workspace in global memory instead of LDS (test/diagnostic) */
     BPMX_OPT_LABELS_GLOBAL = 131072, /* bpmx_labels_device (set with bpmx_set_options): every recording's
                                         workspace in global memory instead of LDS (test/diagnostic) */
-    BPMX_OPT_FLOOR_ONEWG = 1048576   /* the floor after the draft by one 1024-thread workgroup per recording
+    BPMX_OPT_FLOOR_ONEWG = 1048576,  /* the floor after the draft by one 1024-thread workgroup per recording
                                         (k_floor_wm alone) instead of two half-recording workgroups of 512
                                         threads that share a compute unit, with k_floor_wm over the recordings
                                         they hand back (test/diagnostic; the results are bit-identical) */
+    BPMX_OPT_HRVSPEC_DIRECT = 2097152 /* bpmx_hrvspec_device (set with bpmx_set_options): one sincos per term
+                                        instead of one per interval and block of 8 frequencies with a rotation
+                                        along the grid (test/diagnostic; the same tolerance binds both forms) */
 };
 
 /* bpmx_stats counters of the last run with BPMX_OPT_STATS */
@@ -850,9 +854,116 @@ int64_t bpmx_tempo_windows(int64_t nd, int32_t win, int32_t hop);
 int bpmx_tempo_device(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t sr,
                       const bpmx_tempo_params *params, const bpmx_out *in, const bpmx_tempo_out *out, void *stream);
 
+/* The HRV spectrum on the device (bpmx_hrvspec_device): per window of a
+ * recording the Lomb-Scargle periodogram of its RR intervals, the power in a
+ * low- and a high-frequency band and the band peaks.  The reference has no
+ * such stage; this is the definition (csrc/bpmx_hrvspec_core.h states the
+ * per-window arithmetic for host and device, hrv_spectrum.spectrum_ints in
+ * Python the whole of it).
+ *
+ *   Inputs, per recording: the ascending final beats final_idx[0 .. n_final)
+ *       (int32 samples at rate sr, from bpmx_beats_out, in slices at pk_off[f],
+ *       with the beats status) and the recording's envelope length nd, which
+ *       the host takes from frame_offsets and ds as bpmx_pack does.
+ *   Intervals: interval j runs from beat j to beat j + 1; its length is d_j =
+ *       idx[j + 1] - idx[j] samples and its position e_j = idx[j + 1].  It is
+ *       kept iff dmin <= d_j <= dmax.  Its value is y_j = d_j * 1000.0 / sr, ms.
+ *   Windows: bpmx_hrvspec_windows(nd, win, hop) = 0 for nd <= 0, win < 1 or
+ *       hop < 1, 1 for nd <= win, else (nd - win) / hop + 1.  Window w holds the
+ *       kept intervals with w * hop <= e_j < w * hop + win.  Outputs are ragged
+ *       per window; a file's slice starts at the sum of the windows before it.
+ *   Validity: the window code is the first that applies of 1 (few: fewer than
+ *       min_intervals kept intervals), 2 (short: S = e_last - e_first < min_span
+ *       samples), 3 (constant: all y_j equal), 0 (valid).  Every window writes
+ *       n_rr and t_mid = (double)(e_first + e_last) / (2.0 * sr), NaN when n_rr
+ *       is 0.  An invalid window writes NaN for var, lf, hf (and its row of q,
+ *       if asked for) and -1 for both peak indices.
+ *   Spectrum, for a valid window of n kept intervals: s_j = e_j - e_first (exact
+ *       integers), m_y = (sum y_j) / n, u_j = y_j - m_y, w = 1 / n, omega_m =
+ *       om0 + m * dom rad per sample for m < n_freq.  q[m] is the floating-mean
+ *       generalised Lomb-Scargle power normalised to [0, 1]: Zechmeister and
+ *       Kuerster (2009), equations 7 to 20, what scipy.signal.lombscargle(s, u,
+ *       omega, normalize=True, floating_mean=True) computes, with its clamp of
+ *       CC and SS at epsneg (2^-53).  var = sum w u_j^2.
+ *   Bands: index ranges [lf_a, lf_b) and [hf_a, hf_b) on the grid.  lf = scale *
+ *       S * var * sum_{m in LF} q[m], likewise hf.  With scale = df_hz / sr,
+ *       var * q * T is the periodogram's usual A^2 T / 2, summed over the band in
+ *       ms^2; that scaling is a convention, and lf / hf does not depend on it.
+ *       An empty band gives 0.0 and peak -1.  The peak of a band is the index of
+ *       its largest q, the smallest index among equals.
+ *   Per recording: record[0] the count of valid windows, [1] and [2] the means
+ *       of lf and hf over them, [3] the mean of lf / hf over the valid windows
+ *       with hf > 0, [4] the mean of lf / (lf + hf) over those with lf + hf > 0,
+ *       [5 .. 7] reserved NaN.  Means are added in window order and are NaN with
+ *       nothing to average.
+ *   Status: BPMX_HRVSPEC_OK; BPMX_HRVSPEC_NONE when the beats status is not OK
+ *       or n_final < 2 (every window then has code 1 and n_rr 0);
+ *       BPMX_HRVSPEC_OVERFLOW when the slice reaches past cap_peaks (nothing is
+ *       written but the status).
+ *
+ * The order of summation, how tau is removed and how the sines are made are the
+ * kernel's own: one pass over the intervals for six sums per frequency, tau
+ * removed by rotating the sums, and one sincos per interval and block of 8
+ * consecutive frequencies with a rotation by dom * s_j along the grid
+ * (BPMX_OPT_HRVSPEC_DIRECT: one sincos per term).  q agrees with another
+ * statement to (16 n + 8 omega_m S) * 2^-52 / min(CC_tau[m], SS_tau[m]), so a
+ * peak decision between values closer than that may differ.
+ *
+ * Limits: hop >= 1, 1 <= dmin <= dmax, min_intervals >= 3, 1 <= n_freq <= 1024,
+ * 0 <= a <= b <= n_freq for both bands, om0 and dom finite with om0 > 0 and
+ * dom >= 0, else BPMX_E_ARG.  A window holds at most win / dmin + 1 kept
+ * intervals, and a workgroup keeps four doubles of each in LDS:
+ *   32 * (win / dmin + 1) <= 49152 bytes (48 KB),
+ * else BPMX_E_LIMIT, before any launch.  The Python layer's defaults (120 s
+ * windows, 240 BPM at most) need 15 KB. */
+enum bpmx_hrvspec_status {      /* bpmx_hrvspec_out.status */
+    BPMX_HRVSPEC_OK = 0,
+    BPMX_HRVSPEC_NONE = -26,    /* the beats status is not OK, or fewer than two final beats */
+    BPMX_HRVSPEC_OVERFLOW = -27 /* the file's slice reaches past cap_peaks: nothing written but the status */
+};
+
+enum { BPMX_HRVSPEC_RECORD = 8 };
+
+typedef struct {
+    int32_t win, hop;           /* window and step, samples */
+    int32_t dmin, dmax;         /* kept intervals, samples: ceil(60 sr / max_bpm), floor(60 sr / min_bpm) */
+    int32_t min_intervals;      /* a window with fewer kept intervals has code 1 */
+    int32_t min_span;           /* a window spanning fewer samples has code 2: ceil(sr / f0) */
+    int32_t n_freq;             /* grid points */
+    int32_t lf_a, lf_b;         /* the LF band [lf_a, lf_b) on the grid */
+    int32_t hf_a, hf_b;         /* the HF band [hf_a, hf_b) */
+    int32_t reserved;           /* 0 */
+    double om0, dom;            /* omega_m = om0 + m * dom, rad per sample */
+    double scale;               /* df_hz / sr */
+} bpmx_hrvspec_params;
+
+typedef struct {            /* device */
+    int32_t *code, *n_rr;       /* per window; a file's slice starts at the sum of the windows before it */
+    int32_t *lf_peak, *hf_peak; /* per window: grid index or -1 */
+    double *t_mid, *var, *lf, *hf;  /* per window */
+    double *q;                  /* optional [windows][n_freq] */
+    double *record;             /* [n_files][BPMX_HRVSPEC_RECORD] */
+    int32_t *status;            /* [n_files] bpmx_hrvspec_status */
+} bpmx_hrvspec_out;
+
+int64_t bpmx_hrvspec_windows(int64_t nd, int32_t win, int32_t hop);
+
+/* The HRV spectrum of n_files recordings at rate sr from their final beats
+ * (`beats`: final_idx, n_final and status of bpmx_beats_device or
+ * bpmx_marks_device over `tables`, of which pk_off and cap_peaks < 2^31 are
+ * read) and their envelope lengths (frame_offsets and ds, as for bpmx_pack),
+ * asynchronously on `stream`, ordered after the beat stages.  Every pointer of
+ * `out` but q is required.  Nothing beyond the window total of the per-window
+ * arrays or the file count of the per-file ones is written.  Never synchronises
+ * the host; scratch comes from ctx.  n_files = 0 does nothing.  Two launches:
+ * one workgroup per window, one wave per recording; see csrc/k_hrvspec.hip. */
+int bpmx_hrvspec_device(bpmx_ctx *ctx, int32_t n_files, const int64_t *frame_offsets, int32_t ds, int32_t sr,
+                        const bpmx_hrvspec_params *params, const bpmx_packed *tables, const bpmx_beats_out *beats,
+                        const bpmx_hrvspec_out *out, void *stream);
+
 /* bpmx_option bits for the entry points that take no bpmx_params
  * (BPMX_OPT_BEATS_GLOBAL, BPMX_OPT_METRICS_GLOBAL, BPMX_OPT_LABELS_GLOBAL, BPMX_OPT_SCORE_GLOBAL,
- * BPMX_OPT_MARKS_GLOBAL);
+ * BPMX_OPT_MARKS_GLOBAL, BPMX_OPT_HRVSPEC_DIRECT);
  * they hold until set again. */
 int bpmx_set_options(bpmx_ctx *ctx, int32_t options);
 
